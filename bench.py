@@ -15,8 +15,11 @@ N > 1 (one process per GPU under torchrun): the frame is cut into N slices of wh
 (SliceMode=1 style), every rank interpolates the full reference locally, searches/transforms its own slice, and the
 reconstructed bands are all-gathered over RCCL once per frame (strong scaling: total work fixed).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, HIP-event timed on the
-library's stream) and `cpu_baseline` (the oracle port on one host core, bounded sample).
+Prints ONE JSON line (rank 0) with the contract fields. A plain run does only what that line needs: set up, warm up, time
+--steps steps (and write their outputs with --dump-outputs). --full adds everything else to the line: `roofline` (dominant
+kernel, HIP-event timed on the library's stream), the per-stage breakdown, `ref_checksum`, `cpu_baseline` (the real JM or the
+oracle port on one host core, bounded sample), the parity check and the informational legs (loop filter, slice search, real-JM
+encodes, the JM-exact pipeline).
 """
 import argparse
 import ctypes
@@ -377,13 +380,63 @@ def per_partition_predictors(pkg, ctx, lam, prm, mbs):
             "note": "one window walk per distinct centre (the union-window kernel only takes partial partition masks and ranges the fast kernel does not cover)"}
 
 
+DUMP_BUDGET = 64 * 1000 * 1000        # bytes, all --dump-outputs files together
+
+
+def dump_outputs(ctx, d, n, me):
+    """--dump-outputs: what the last timed step handed back, as float32 / float64 .npy files under `d` (float64 where an integer field may
+    not fit float32's 24-bit mantissa). The reference picture the step left (its reconstruction) is written whole; the per-macroblock arrays
+    of this rank's macroblocks (rank 0 writes) -- motion search results (`me`: the independent-macroblocks search), decided modes, coded block patterns and
+    the frame stage's coefficient lists, expanded as jmhip_residual_download expands them (zero past each list's length) -- on a fixed,
+    seeded sample of macroblocks when everything would not fit DUMP_BUDGET (mb_index.npy names them)."""
+    os.makedirs(d, exist_ok=True)
+    ry, ru, rv, _, _ = ctx.ref_device_planes_ro(0)
+    planes = {}
+    for name, ptr, rows, cols in (("recon_y", ry, H, W), ("recon_u", ru, H // 2, W // 2), ("recon_v", rv, H // 2, W // 2)):
+        host = np.zeros((rows, cols), np.uint8)
+        ctx.copy_from_device(ptr, host)
+        planes[name] = host.astype(np.float32)
+    rd = ctx.residual_download(n, want_results=False)
+    rec = ctx.residual_records(n)
+    live = np.arange(16)[None, None, :] < rec["cnt"][:, :, None]
+    lev, run = np.where(live, rec["lev"], 0), np.where(live, rec["run"], 0)
+    lev[:, 16:] *= (rec["ac_zeroed"] == 0).repeat(4, axis=1)[:, :, None]          # _CHROMA_COEFF_COST_ thresholding: AC levels read 0
+    dc_live = np.arange(4)[None, None, :] < rec["dc_cnt"][:, :, None]
+    f32, f64 = np.float32, np.float64
+    per_mb = {"mb_mode": (rd["modes"]["mode"], f32), "mb_b8mode": (rd["modes"]["b8mode"], f32), "mb_cbp": (rd["cbp"], f64), "mb_cbp_blk": (rd["cbp_blk"], f64),
+              "luma_levels": (lev[:, :16], f32), "luma_runs": (run[:, :16], f32), "luma_coeff_cost": (rec["coeff_cost"], f64),
+              "luma_nonzero": ((rec["nonzero"][:, None].astype(np.int32) >> np.arange(16)) & 1, f32), "luma_fadjust": (rec["fadj_y"], f32),
+              "chroma_ac_levels": (lev[:, 16:].reshape(n, 2, 4, 16), f32), "chroma_ac_runs": (run[:, 16:].reshape(n, 2, 4, 16), f32),
+              "chroma_dc_levels": (np.where(dc_live, rec["dc_lev"], 0), f32), "chroma_dc_runs": (np.where(dc_live, rec["dc_run"], 0), f32),
+              "chroma_fadjust": (rec["fadj_c"], f32), "chroma_ret": (rec["ret"], f64), "chroma_cbp_blk": (rec["cbp_blk"], f64), "chroma_cbp_clear": (rec["cbp_clear"], f64)}
+    if me:
+        res = ctx.me_results(n)
+        per_mb.update({"me_mv": (res["mv"], f32), "me_cost": (res["cost"], f64), "me_mv_int": (res["mv_int"], f32), "me_cost_int": (res["cost_int"], f64)})
+    per_mb_bytes = sum(np.dtype(t).itemsize * a[0].size for a, t in per_mb.values())
+    room = DUMP_BUDGET - sum(p.nbytes for p in planes.values()) - 128 * (len(planes) + len(per_mb) + 1)      # (+ one .npy header per file)
+    pick = np.arange(n)
+    if per_mb_bytes * n > room:
+        pick = np.sort(np.random.default_rng(20261016).choice(n, size=max(1, room // (per_mb_bytes + 8)), replace=False))
+    out = dict(planes, mb_index=pick.astype(f64))
+    out.update({k: np.ascontiguousarray(a[pick], dtype=t) for k, (a, t) in per_mb.items()})
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def main():
     global W, H_SRC, H, MBW, MBH
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--cpu-mbs", type=int, default=4 * MBW, help="macroblocks in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure: HIP-event stage timers and the roofline, the per-stage breakdown "
+                         "(three extra steps), ref_checksum, and on one GPU the CPU baselines, the parity check against the oracle, the loop filter, "
+                         "the slice search, the real-JM encodes and the JM-exact pipeline. Off: the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (reconstructed picture; motion search results, modes and coefficient "
+                         "lists of the macroblocks of rank 0) to DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed, seeded macroblock sample beyond)")
+    ap.add_argument("--cpu-mbs", type=int, default=4 * MBW, help="with --full: macroblocks in the CPU baseline sample (0 = skip)")
     ap.add_argument("--clip", choices=["translation", "noise"], default="translation",
                     help="translation = SURVEY 8(d)'s clip (default, the metric's workload); noise = its adversarial i.i.d. clip, for information only")
     ap.add_argument("--chroma-planes", action="store_true",
@@ -412,6 +465,8 @@ def main():
                          "(4K, FullSearch +-32, slices sharded across the GPUs with the reference picture gathered once per frame), the configuration "
                          "BASELINE names for more than one GPU: the default at --gpus > 1 (north_star's scaling target is quoted on 4K)")
     args = ap.parse_args()
+    if not args.full:
+        args.cpu_mbs = 0                              # the CPU baselines, the parity check and the informational legs are --full's
     if args.size is None:
         args.size = "1080p" if args.gpus == 1 else "2160p"
     if args.size == "2160p":
@@ -577,54 +632,55 @@ def main():
     for k in range(args.warmup):
         step(k)
     fence()
-    # timed region: HIP events only round the dominant kernel (roofline.avg_launch_ms); the per-stage breakdown comes from
+    # timed region. --full: HIP events only round the dominant kernel (roofline.avg_launch_ms); the per-stage breakdown comes from
     # three extra, untimed steps afterwards, so that eleven more event records per step do not sit in the measurement
-    ctx.timing_enable(True)
-    ctx.timing_select(["me_int"])
-    ctx.timing_read()
+    if args.full:
+        ctx.timing_enable(True)
+        ctx.timing_select(["me_int"])
+        ctx.timing_read()
     t0 = time.perf_counter()
     for k in range(args.steps):
         step(args.warmup + k)
     fence()
     elapsed = time.perf_counter() - t0
-    stage_me = ctx.timing_read()
-    ctx.timing_select(list(pkg.STAGES))
-    prev_ref_host = None
-    for k in range(3):
-        if k == 2 and world == 1 and args.cpu_mbs > 0:          # the reference picture the last step searches: kept for the parity check
-            ctx.sync()
-            ry, _, _, _, _ = ctx.ref_device_planes_ro(0)
-            prev_ref_host = np.zeros((H, W), np.uint8)
-            ctx.copy_from_device(ry, prev_ref_host)
-        step(args.warmup + args.steps + k)
-    fence()
-    stage = ctx.timing_read()
-    stage["me_int"] = stage_me["me_int"]
-    ctx.timing_enable(False)
+    if args.full:
+        stage_me = ctx.timing_read()
+    if args.dump_outputs and (rank == 0 or solo) and n:
+        dump_outputs(ctx, args.dump_outputs, n, me=not args.exact)
+    if args.full:
+        ctx.timing_select(list(pkg.STAGES))
+        prev_ref_host = None
+        for k in range(3):
+            if k == 2 and world == 1 and args.cpu_mbs > 0:          # the reference picture the last step searches: kept for the parity check
+                ctx.sync()
+                ry, _, _, _, _ = ctx.ref_device_planes_ro(0)
+                prev_ref_host = np.zeros((H, W), np.uint8)
+                ctx.copy_from_device(ry, prev_ref_host)
+            step(args.warmup + args.steps + k)
+        fence()
+        stage = ctx.timing_read()
+        stage["me_int"] = stage_me["me_int"]
+        ctx.timing_enable(False)
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # checksum of the reference picture the last step produced: the same for every N (strong scaling: the same frames are coded,
-    # only sharded differently) -- tests/test_bench_ranks.py compares N = 1 with a rehearsed N = 2
-    ctx.sync()
-    ry, ru, rv, _, _ = ctx.ref_device_planes_ro(0)
-    ref_sum = 0
-    for ptr, rows, cols in ((ry, H, W), (ru, H // 2, W // 2), (rv, H // 2, W // 2)):
-        host = np.zeros((rows, cols), np.uint8)
-        ctx.copy_from_device(ptr, host)
-        ref_sum = (ref_sum * 1000003 + int(host.astype(np.int64).sum()) + int((host.astype(np.int64) * (np.arange(cols) % 251 + 1)).sum())) % (1 << 61)
+    if args.full:
+        # checksum of the reference picture the last step produced: the same for every N (strong scaling: the same frames are coded,
+        # only sharded differently) -- tests/test_bench_ranks.py compares N = 1 with a rehearsed N = 2
+        ctx.sync()
+        ry, ru, rv, _, _ = ctx.ref_device_planes_ro(0)
+        ref_sum = 0
+        for ptr, rows, cols in ((ry, H, W), (ru, H // 2, W // 2), (rv, H // 2, W // 2)):
+            host = np.zeros((rows, cols), np.uint8)
+            ctx.copy_from_device(ptr, host)
+            ref_sum = (ref_sum * 1000003 + int(host.astype(np.int64).sum()) + int((host.astype(np.int64) * (np.arange(cols) % 251 + 1)).sum())) % (1 << 61)
 
     if rank == 0 or solo:
         total_mbs = MBW * MBH * args.steps
         ms_step = elapsed / args.steps * 1e3
-        me_ms, me_launches = stage["me_int"]
-        me_avg_ms = me_ms / max(1, me_launches)
-        achieved = ME_BYTES_PER_MB * n / (me_avg_ms * 1e-3) / 1e9 if me_launches else 0.0
-        sad_ops = (2 * R + 1) ** 2 * 256 * n / (me_avg_ms * 1e-3) if me_launches else 0.0
-        valu_floor_ms = n * ((2 * R + 1) ** 2 / 64.0) * VALU_NS_PER_WAVE_CANDIDATE / N_SIMD * 1e-6
         workload = ("1920x1080 (coded 1920x1088, 8160 MBs)" if args.size == "1080p" else "3840x2160 (32400 MBs)") + \
             " YUV420 P-frames, baseline tools, FullSearch +-32, 41 partitions, SAD full-pel + SATD sub-pel, dct_4x4 + dct_chroma, QP %d, 1 reference; " % QP + \
             "16 luma quarter-pel planes per reference, chroma eighth-pel samples " + ("from 2 x 64 planes; " if args.chroma_planes else "computed in MC; ") + \
@@ -634,30 +690,38 @@ def main():
         out = {
             "metric": "macroblocks/sec (full-search ME + DCT/quant), %s; bit-exact MV+coeff vs JM" % (
                 "1080p" if args.size == "1080p" else "2160p (BASELINE configs[3]: the 4K picture sharded by slices; the metric's own 1080p is the --gpus 1 default)"),
-            "metric_note": "predictors are an INPUT of this pipeline (one per macroblock, SURVEY 8(d)'s independent-MBs recipe); `parity_check` compares a sample of the "
-                           "last step with the oracle; `slice_search` gives the JM-exact form (predictors + decision on the device, raster-order dependencies kept)",
+            "metric_note": "predictors are an INPUT of this pipeline (one per macroblock, SURVEY 8(d)'s independent-MBs recipe); with --full, `parity_check` compares a sample of the "
+                           "last step with the oracle and `slice_search` gives the JM-exact form (predictors + decision on the device, raster-order dependencies kept)",
             "value": round(total_mbs / elapsed, 1), "unit": "macroblocks/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": workload,
                        "slices": world, "parallelism": "slice%d" % world},
-            "roofline": {"kernel": "me_int_pair_kernel (integer full search, all 41 partitions)", "bound": "valu",
-                         "achieved": round(sad_ops / 1e12, 3), "peak": round(sad_ops / 1e12 * me_avg_ms / valu_floor_ms, 3) if me_launches else None,
-                         "unit": "T abs-diff/s", "frac": round(valu_floor_ms / me_avg_ms, 4) if me_launches else None,
-                         "traffic": pmc_traffic("me_int_pair_kernel", n), "avg_launch_ms": round(me_avg_ms, 4), "units_per_launch": n,
-                         "peak_is": "a MODEL, not a guide constant: the time the search's irreducible work -- per candidate 64 v_sad_u8, 25 + 40 adds, "
-                                    "20.5 v_min3 -- takes at issue rates measured on this chip (tools/ubench/valu_rate2.hip -> "
-                                    "profiles/r01_valu_issue_rates.txt: v_sad_u8 / v_min3_u32 1.89 ns, v_add_u32 1.04 ns per wave-instruction per SIMD, "
-                                    "1024 SIMDs); full search is about 1e3 integer ops per compulsory byte (SURVEY 8(d)), so HBM is not the roof that binds",
-                         "valu_model": {"model_floor_ms": round(valu_floor_ms, 4), "ns_per_wave_candidate_row": round(VALU_NS_PER_WAVE_CANDIDATE, 1), "simds": N_SIMD},
-                         "hbm": {"achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                                 "algorithmic_bytes_per_unit": ME_BYTES_PER_MB,
-                                 "traffic_note": "traffic = (FETCH_SIZE + WRITE_SIZE) KB x 1024 per launch from profiles/r02_final_pmc_*.csv, raw: the guide's x2 "
-                                                 "FETCH_SIZE correction is calibrated for 16 B/lane streaming reads and this kernel reads dwords, so it is not applied"}},
-            "stages_ms_per_launch": {k: round(v[0] / max(1, v[1]), 4) for k, v in stage.items()},
-            "ref_checksum": ref_sum,
         }
-        if world == 1:
+        if args.full:
+            me_ms, me_launches = stage["me_int"]
+            me_avg_ms = me_ms / max(1, me_launches)
+            achieved = ME_BYTES_PER_MB * n / (me_avg_ms * 1e-3) / 1e9 if me_launches else 0.0
+            sad_ops = (2 * R + 1) ** 2 * 256 * n / (me_avg_ms * 1e-3) if me_launches else 0.0
+            valu_floor_ms = n * ((2 * R + 1) ** 2 / 64.0) * VALU_NS_PER_WAVE_CANDIDATE / N_SIMD * 1e-6
+            out.update({
+                "roofline": {"kernel": "me_int_pair_kernel (integer full search, all 41 partitions)", "bound": "valu",
+                             "achieved": round(sad_ops / 1e12, 3), "peak": round(sad_ops / 1e12 * me_avg_ms / valu_floor_ms, 3) if me_launches else None,
+                             "unit": "T abs-diff/s", "frac": round(valu_floor_ms / me_avg_ms, 4) if me_launches else None,
+                             "traffic": pmc_traffic("me_int_pair_kernel", n), "avg_launch_ms": round(me_avg_ms, 4), "units_per_launch": n,
+                             "peak_is": "a MODEL, not a guide constant: the time the search's irreducible work -- per candidate 64 v_sad_u8, 25 + 40 adds, "
+                                        "20.5 v_min3 -- takes at issue rates measured on this chip (tools/ubench/valu_rate2.hip -> "
+                                        "profiles/r01_valu_issue_rates.txt: v_sad_u8 / v_min3_u32 1.89 ns, v_add_u32 1.04 ns per wave-instruction per SIMD, "
+                                        "1024 SIMDs); full search is about 1e3 integer ops per compulsory byte (SURVEY 8(d)), so HBM is not the roof that binds",
+                             "valu_model": {"model_floor_ms": round(valu_floor_ms, 4), "ns_per_wave_candidate_row": round(VALU_NS_PER_WAVE_CANDIDATE, 1), "simds": N_SIMD},
+                             "hbm": {"achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                                     "algorithmic_bytes_per_unit": ME_BYTES_PER_MB,
+                                     "traffic_note": "traffic = (FETCH_SIZE + WRITE_SIZE) KB x 1024 per launch from profiles/r02_final_pmc_*.csv, raw: the guide's x2 "
+                                                     "FETCH_SIZE correction is calibrated for 16 B/lane streaming reads and this kernel reads dwords, so it is not applied"}},
+                "stages_ms_per_launch": {k: round(v[0] / max(1, v[1]), 4) for k, v in stage.items()},
+                "ref_checksum": ref_sum,
+            })
+        if args.full and world == 1:
             # the HBM-bound stages against the same 8 TB/s, from SURVEY 8(d)'s algorithmic bytes at this build's 8-bit samples:
             # luma planes (1 read + 16 written) x padded plane; chroma 2 x (1 + 64) x padded plane; transform/quant/recon per macroblock
             # cur + pred 768 B in, levels 384 x 4 B + recon 384 B out
@@ -707,7 +771,7 @@ def main():
             # synthetic predictor per macroblock, then the frame stage from that decision), in a process of its own
             try:
                 import subprocess
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--exact", "--steps", "8", "--warmup", "3", "--cpu-mbs", "0"], capture_output=True, text=True, timeout=300)
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--exact", "--full", "--steps", "8", "--warmup", "3", "--cpu-mbs", "0"], capture_output=True, text=True, timeout=300)
                 ex = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 out["jm_exact_pipeline"] = {"macroblocks_per_s": ex["value"], "ms_per_step": ex["ms_per_step"], "slice_search_ms": ex["roofline"]["slice_search_ms"],
                                             "sweeps_last_steps": ex["roofline"]["sweeps_last_steps"], "ref_checksum": ex.get("ref_checksum"),
@@ -722,6 +786,7 @@ def main():
                                   "jmhip_residual_frame, band exchange. The metric's own workload is the default run (independent macroblocks)")
             out["config"]["workload"] = workload.replace("predictor field (16,-16)+U{-8..8} qpel per MB", "JM's own predictors (SetMotionVectorPredictor in raster order, on the device)")
             out["config"]["slices"] = max(world, args.exact_slices or 1)
+        if args.exact and args.full:
             me_ms, me_launches = stage["me_int"]
             out["roofline"] = {"kernel": "jmhip_p_slice_search (x_sim_kernel + me_int_pair_kernel<list> + me_sub_kernel<list>, sweeps to the fixpoint)", "bound": "valu",
                                "achieved": round((2 * R + 1) ** 2 * 256 * n / (me_ms / max(1, me_launches) * 1e-3) / 1e12, 3) if me_launches else None,

@@ -1,10 +1,11 @@
-"""Pins the oracle: the C restatement (oracle/jmo_*.c) is swapped INTO the real JM encoder built from
-/root/reference (oracle/tap/swap_oracle.c, symbol interposition) and the bitstream + reconstruction JM
-writes must stay byte-identical to the unmodified encoder's, for every shipped cfg x SearchMode and a set
-of option variants. The first case is the reference's own known-answer pair bin/test.264 + bin/test_rec.yuv.
+"""Pins the oracle: the C restatement (oracle/jmo_*.c) is swapped INTO the real JM encoder (oracle/tap/swap_oracle.c,
+symbol interposition) and the bitstream + reconstruction JM writes must stay byte-identical to the unmodified encoder's,
+for every shipped cfg x SearchMode and a set of option variants. The first case is the reference's own known-answer pair
+test.264 + test_rec.yuv.
 
-Container only: needs /root/reference (sources + bin/ fixtures) and `make -C oracle ref`.
-Skipped on the GPU box, where neither exists.
+Inputs are the data fixtures under tests/golden/jm_bin/ (the reference encoder's sample configurations with comments and
+blank lines removed, its QCIF clips, the known-answer pair under expected/). The encoders are oracle/_ref/jm_plain and
+jm_swap, which build() compiles from the reference sources where those are present; without them the tests skip.
 """
 import hashlib
 import os
@@ -14,26 +15,22 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+FIXTURES = os.path.join(ROOT, "tests", "golden", "jm_bin")
 RDIR = os.path.join(ROOT, "oracle", "_ref")
 
 pytestmark = [
     pytest.mark.reference,
-    pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "bin")), reason="/root/reference not present"),
+    pytest.mark.skipif(not all(os.path.exists(os.path.join(RDIR, e)) for e in ("jm_plain", "jm_swap")),
+                       reason="oracle/_ref/jm_plain and jm_swap not built (build() makes them where the reference sources are)"),
 ]
 
 
 @pytest.fixture(scope="module")
 def rundir(tmp_path_factory):
-    if not (os.path.exists(os.path.join(RDIR, "jm_swap")) and os.path.exists(os.path.join(RDIR, "jm_plain"))):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "-j8", "all", "ref"], check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     d = tmp_path_factory.mktemp("jmrun")
-    for f in os.listdir(os.path.join(REF, "bin")):
+    for f in os.listdir(FIXTURES):
         if f.endswith(".cfg") or f.endswith(".yuv"):
-            shutil.copy(os.path.join(REF, "bin", f), d / f)
-    for f in ("test.264", "test_rec.yuv"):
-        os.remove(d / f) if os.path.exists(d / f) else None
+            shutil.copy(os.path.join(FIXTURES, f), d / f)
     return d
 
 
@@ -57,7 +54,7 @@ def test_known_answer_with_oracle_swapped_in(rundir):
     """default encoder.cfg: the reference ships the expected bitstream and reconstruction."""
     _run("jm_swap", rundir, [])
     for f in ("test.264", "test_rec.yuv"):
-        with open(rundir / f, "rb") as a, open(os.path.join(REF, "bin", f), "rb") as b:
+        with open(rundir / f, "rb") as a, open(os.path.join(FIXTURES, "expected", f), "rb") as b:
             assert a.read() == b.read(), f
 
 

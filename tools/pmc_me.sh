@@ -9,8 +9,8 @@ mkdir -p $out
 cd /tmp
 for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM SQ_INSTS_LDS" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT" "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS" "GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_IFETCH"; do
   n=$(echo $set | tr ' ' '_' | cut -c1-40)
-  timeout -k 10 200 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/pers_$n -- python3 $root/bench.py --steps 2 --warmup 1 --cpu-mbs 0 > $out/pers_$n.log 2>&1 || echo "failed: $set"
-  JMHIP_ME_KERNEL=pair timeout -k 10 200 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/pair_$n -- python3 $root/bench.py --steps 2 --warmup 1 --cpu-mbs 0 > $out/pair_$n.log 2>&1 || echo "failed: $set"
+  timeout -k 10 200 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/pers_$n -- python3 $root/bench.py --full --steps 2 --warmup 1 --cpu-mbs 0 > $out/pers_$n.log 2>&1 || echo "failed: $set"
+  JMHIP_ME_KERNEL=pair timeout -k 10 200 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/pair_$n -- python3 $root/bench.py --full --steps 2 --warmup 1 --cpu-mbs 0 > $out/pair_$n.log 2>&1 || echo "failed: $set"
 done
 cd $root
 python3 - "$out" <<'PY'

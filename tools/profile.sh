@@ -12,9 +12,9 @@ root=$PWD
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --steps 20 --warmup 3 --cpu-mbs 0 > $out/bench_under_rocprof.json 2> $out/stats.log
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -- python3 $root/bench.py --steps 3 --warmup 1 --cpu-mbs 0 > $out/pmc_fetch.log 2>&1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/pmc_write -- python3 $root/bench.py --steps 3 --warmup 1 --cpu-mbs 0 > $out/pmc_write.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --full --steps 20 --warmup 3 --cpu-mbs 0 > $out/bench_under_rocprof.json 2> $out/stats.log
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -- python3 $root/bench.py --full --steps 3 --warmup 1 --cpu-mbs 0 > $out/pmc_fetch.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/pmc_write -- python3 $root/bench.py --full --steps 3 --warmup 1 --cpu-mbs 0 > $out/pmc_write.log 2>&1
 cd $root
 python3 - "$out" <<'PY'
 import csv, glob, json, re, sys, collections
