@@ -1,6 +1,6 @@
 // frame.hip -- frame stage after the search: MC prediction -> residual -> transform/quant -> thresholding -> recon.
 //
-// Device-side restatement of the inter path of LumaResidualCoding / ChromaResidualCoding for P macroblocks without
+// Device-side restatement of the inter path of LumaResidualCoding / ChromaResidualCoding for P macroblocks, with the 4x4 or
 // the 8x8 transform (the step between ME and transform):
 //   SetModesAndRefframe + LumaResidualCoding8x8   lencod/src/macroblock.c:1009-1300  (4x4 loop :1039-1110,
 //                                                  _LUMA_COEFF_COST_ thresholding :1236-1258)
@@ -304,6 +304,9 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
   // same sample values are computed in mc_kernel from the integer chroma pictures (reference slots 0..7)
   bool chroma_fly = false;
   const unsigned used_refs = c->me_ref_mask | (c->fr_bi_n ? c->fr_bi_mask : 0u);      // list 0 of the search stage, list 1 of jmhip_frame_bipred_set
+  // explicit weights are kept per slot 0..15, the list-0 side of a B macroblock's weight pairs per slot 0..3
+  if (c->fr_wp.enable && (used_refs >> 16)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: explicit weighted prediction from reference slots 0..15 only");
+  if (c->fr_bi_n && (c->me_ref_mask >> 4)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: B macroblocks predict from list-0 reference slots 0..3 only");
   for (size_t k = 0; k < c->refs.size(); k++)
     if ((used_refs >> k) & 1) {
       if (!c->refs[k].has_luma_sub) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: quarter-pel planes of a used reference not built (jmhip_interp_luma)");
@@ -349,20 +352,28 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
   F.wp_on = c->fr_wp.enable ? 1 : 0; F.wp_lround = c->fr_wp.luma_round; F.wp_ldenom = c->fr_wp.luma_denom; F.wp_cround = c->fr_wp.chroma_round; F.wp_cdenom = c->fr_wp.chroma_denom;
   for (int k = 0; k < 16; k++) for (int q = 0; q < 3; q++) { F.wp_w[k][q] = c->fr_wp.weight[k][q]; F.wp_o[k][q] = c->fr_wp.offset[k][q]; }
 
-  // the common case -- 4:2:0, 4x4 transform everywhere -- is ONE kernel that keeps the tiles on the CU and leaves a dense record per macroblock
-  // (tq.hip frame_fused_kernel); JMHIP_FRAME_FUSED=0 keeps the separate kernels (also taken by 4:2:2, 4:0:0 and 8x8-transform macroblocks)
-  bool fused = F.yuv == JMHIP_YUV420 && !any_t8 && quants[0].adapt_rnd_weight >= 0 && quants[0].adapt_rnd_weight < 32768 &&
-               quants[1].adapt_rnd_weight >= 0 && quants[1].adapt_rnd_weight < 32768;
+  // 4:2:0 is ONE kernel that keeps the tiles on the CU and leaves a dense record per macroblock (tq.hip frame_fused_kernel); a picture with
+  // 8x8-transform macroblocks takes its T8 instantiation, which adds a jmhip_mb_residual8 side record per macroblock. JMHIP_FRAME_FUSED=0
+  // keeps the separate kernels (also taken by 4:2:2 and 4:0:0)
+  bool fused = F.yuv == JMHIP_YUV420 && quants[0].adapt_rnd_weight >= 0 && quants[0].adapt_rnd_weight < 32768 &&
+               quants[1].adapt_rnd_weight >= 0 && quants[1].adapt_rnd_weight < 32768 &&
+               (!any_t8 || (quants[3].adapt_rnd_weight >= 0 && quants[3].adapt_rnd_weight < 32768));
   if (const char *e = getenv("JMHIP_FRAME_FUSED")) if (!strcmp(e, "0")) fused = false;
+  if (fused && any_t8 && c->fr_rec8_capacity < n) {
+    if (c->fr_rec8) JM_HIP_CHECK(c, hipFree(c->fr_rec8));
+    c->fr_rec8 = nullptr; c->fr_rec8_capacity = 0;
+    if (hipMalloc(&c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "8x8-transform side records");
+    c->fr_rec8_capacity = n;
+  }
   if (fused) {
     jm_stage_begin(c, JMHIP_STAGE_MC);
-    rc = jm_launch_frame_fused(c, &F, c->me_jobs_dev, c->me_res_dev, modes_in_dev, modes_out_dev, c->fr_quant, c->fr_rec, coded_dev, n);
+    rc = jm_launch_frame_fused(c, &F, c->me_jobs_dev, c->me_res_dev, modes_in_dev, modes_out_dev, c->fr_quant, c->fr_rec, coded_dev, n, any_t8 ? c->fr_rec8 : nullptr);
     jm_stage_end(c, JMHIP_STAGE_MC);                  // (the TQ stage has no launch of its own here: its time reads 0)
     if (rc) return rc;
-    c->fr_n = n; c->rec_valid = true; c->fr_fused = true; c->pred_valid = c->keep_pred;
+    c->fr_n = n; c->rec_valid = true; c->fr_fused = true; c->fr_fused8 = any_t8; c->pred_valid = c->keep_pred;
     return JMHIP_OK;
   }
-  c->fr_fused = false; c->pred_valid = false;
+  c->fr_fused = false; c->fr_fused8 = false; c->pred_valid = false;
   jm_stage_begin(c, JMHIP_STAGE_MC);
   mc_kernel<<<jm_xcd_grid(n), 64, 0, c->stream>>>(F, (const jmhip_me_mb *)c->me_jobs_dev, (const jmhip_me_result *)c->me_res_dev, modes_in_dev, modes_out_dev,
                                                   (jmhip_tq_job *)c->fr_jobs_y, (jmhip_tq_job *)c->fr_jobs_c, n);
@@ -389,9 +400,14 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
   if (!c) return JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_download: more macroblocks requested than processed");
   std::vector<JmMbRes> recs;
+  std::vector<jmhip_mb_residual8> recs8;
   if (c->fr_fused && (luma || (chroma && c->Wc))) {
     recs.resize(n);
     JM_HIP_CHECK(c, hipMemcpyAsync(recs.data(), c->fr_rec, sizeof(JmMbRes) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (c->fr_fused8 && luma) {
+      recs8.resize(n);
+      JM_HIP_CHECK(c, hipMemcpyAsync(recs8.data(), c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
   } else {
     if (luma) JM_HIP_CHECK(c, hipMemcpyAsync(luma, c->fr_res_y, sizeof(jmhip_tq_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (chroma && c->Wc) JM_HIP_CHECK(c, hipMemcpyAsync(chroma, c->fr_res_c, sizeof(jmhip_tq_result) * (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
@@ -416,7 +432,19 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
         for (int k = 0; k < R.cnt[b]; k++) { o.levels[b][k] = R.lev[b][k]; o.runs[b][k] = R.run[b][k]; }
         o.coeff_cost[b] = R.coeff_cost[b]; o.nonzero[b] = (R.nonzero >> b) & 1;
       }
-      for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) { o.recon[y][x] = R.recon_y[y][x]; if (c->fr_quant_host[0].adaptive_rounding) o.fadjust[y][x] = R.fadj_y[y][x]; }
+      const bool t8 = !recs8.empty() && recs8[i].transform8x8;
+      for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) { o.recon[y][x] = R.recon_y[y][x]; if (c->fr_quant_host[t8 ? 3 : 0].adaptive_rounding) o.fadjust[y][x] = R.fadj_y[y][x]; }
+      if (t8) {                                        // what tq_luma8x8_kernel writes: cofAC in levels8 (one list) or in rows 4*b8.. of levels (CAVLC)
+        const jmhip_mb_residual8 &R8 = recs8[i];
+        for (int b8 = 0; b8 < 4; b8++) {
+          if (R8.interleaved)
+            for (int k = 0; k < 4; k++)
+              for (int e = 0; e < R8.cnt[b8][k]; e++) { o.levels[4 * b8 + k][e] = R8.lev[b8][16 * k + e]; o.runs[4 * b8 + k][e] = R8.run[b8][16 * k + e]; }
+          else
+            for (int e = 0; e < R8.cnt[b8][0]; e++) { o.levels8[b8][e] = R8.lev[b8][e]; o.runs8[b8][e] = R8.run[b8][e]; }
+          o.coeff_cost[b8] = R8.coeff_cost[b8]; o.nonzero[b8] = R8.nonzero[b8];
+        }
+      }
     }
     for (int uv = 0; uv < 2 && chroma && c->Wc; uv++) {
       jmhip_tq_result &o = chroma[2 * i + uv];
@@ -438,6 +466,18 @@ extern "C" int jmhip_residual_records_download(jmhip_ctx *c, jmhip_mb_residual *
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage did not take the fused 4:2:0 kernel (use jmhip_residual_download)");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec, sizeof(jmhip_mb_residual) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return JMHIP_OK;
+}
+
+extern "C" int jmhip_residual_records8_download(jmhip_ctx *c, jmhip_mb_residual8 *records, int n)
+{
+  if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records8_download: NULL") : JMHIP_ERR_ARG;
+  if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records8_download: more macroblocks requested than processed");
+  if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records8_download: the last frame stage did not take the fused 4:2:0 kernel (use jmhip_residual_download)");
+  if (!c->fr_fused8) { memset(records, 0, sizeof(jmhip_mb_residual8) * (size_t)n); return JMHIP_OK; }     // no 8x8-transform macroblock
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }

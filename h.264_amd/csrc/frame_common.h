@@ -101,4 +101,4 @@ typedef jmhip_mb_residual JmMbRes;
 static_assert(sizeof(JmMbRes) % 16 == 0, "records are copied out of LDS as 16-byte pieces");
 
 int jm_launch_frame_fused(jmhip_ctx *c, const void *frame_dev, const void *mbs, const void *me, const void *modes_in, void *modes_out,
-                          const void *quants, void *records, void *coded, int n);
+                          const void *quants, void *records, void *coded, int n, void *records8);   // records8: NULL, or the 8x8-transform instantiation's side records

@@ -39,6 +39,7 @@ extern "C" int jmhip_sizeof(int which)
   case 20: return (int)sizeof(jmhip_mb_bipred);
   case 21: return (int)sizeof(jmhip_frame_bw);
   case 22: return (int)sizeof(jmhip_mb_residual);
+  case 23: return (int)sizeof(jmhip_mb_residual8);
   default: return -1;
   }
 }
@@ -123,7 +124,7 @@ extern "C" void jmhip_ctx_destroy(jmhip_ctx *c)
   for (auto e : c->pin_evt) (void)hipEventDestroy(e);
   (void)hipFree(c->stage_dev); (void)hipFree(c->me_jobs_dev); (void)hipFree(c->me_res_dev); (void)hipFree(c->ref_ptrs_dev); (void)hipFree(c->me_idx_dev); (void)hipFree(c->surf_dev); (void)hipFree(c->surf_jobs_dev);
   (void)hipFree(c->tq_jobs_dev); (void)hipFree(c->tq_res_dev); (void)hipFree(c->tq_quant_dev);
-  (void)hipFree(c->fr_bi); (void)hipFree(c->fr_rec); (void)hipFree(c->fr_blk_ref); (void)hipFree(c->fr_jobs_y); (void)hipFree(c->fr_jobs_c); (void)hipFree(c->fr_res_y); (void)hipFree(c->fr_res_c);
+  (void)hipFree(c->fr_bi); (void)hipFree(c->fr_rec); (void)hipFree(c->fr_rec8); (void)hipFree(c->fr_blk_ref); (void)hipFree(c->fr_jobs_y); (void)hipFree(c->fr_jobs_c); (void)hipFree(c->fr_res_y); (void)hipFree(c->fr_res_c);
   jm_slice_state_free(c);
   jm_xslice_free(c);
   (void)hipFree(c->dbk_dev); (void)hipFree(c->dbr_dev); (void)hipFree(c->fr_quant); (void)hipFree(c->fr_modes); (void)hipFree(c->rec_y); (void)hipFree(c->pred_y); (void)hipFree(c->pred_u); (void)hipFree(c->pred_v); (void)hipFree(c->rec_u); (void)hipFree(c->rec_v);

@@ -57,6 +57,9 @@ struct jmhip_ctx {
   int fr_capacity = 0, fr_n = 0;
   void *fr_rec = nullptr;                             // fused frame stage: one JmMbRes record per macroblock (frame_common.h)
   bool fr_fused = false;                              // the last jmhip_residual_frame took the fused kernel: results live in fr_rec
+  void *fr_rec8 = nullptr;                            // ... and one jmhip_mb_residual8 per macroblock when the picture has 8x8-transform macroblocks
+  int fr_rec8_capacity = 0;
+  bool fr_fused8 = false;                             // the last fused stage was the 8x8-transform instantiation: fr_rec8 holds its side records
   void *fr_blk_ref = nullptr;                         // [n][4] reference slot per 8x8 block (frame stage fed from the slice search)
   bool fr_slices_t8 = false;                          // ... and some of them may carry the 8x8-transform flag (Transform8x8Mode in the slice search)
   bool fr_from_slices = false;                        // modes + per-block references of the frame stage were left on the device by jmhip_slice_to_frame

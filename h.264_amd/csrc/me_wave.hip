@@ -2808,7 +2808,8 @@ static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, i
   unsigned mask = 0;
   SlotMap sm{};
   for (int r = 0; r < num_refs; r++) {
-    if (ref_slot[r] < 0 || ref_slot[r] >= (int)c->refs.size() || ref_slot[r] >= 8) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame: reference slots 0..7");
+    // every allocated slot: the 0..7 limit of the chroma samples computed without the eighth-pel planes is jmhip_residual_frame's to check
+    if (ref_slot[r] < 0 || ref_slot[r] >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame: reference slot outside the context");
     sm.s[r] = ref_slot[r]; mask |= 1u << ref_slot[r];
   }
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));

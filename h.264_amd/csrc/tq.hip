@@ -667,9 +667,23 @@ __global__ __launch_bounds__(256) void tq_chroma420_kernel(const jmhip_tq_job *_
 // b8*4+b4, so a DPP quad is an 8x8 block), in the chroma phase lanes 0..31 own the four Cb / four Cr blocks of each macroblock (a quad per
 // component, as tq_chroma420_kernel); all 64 lanes fetch the chroma prediction.
 // Same arithmetic, line for line, as the kernels it replaces (they stay for 4:2:2, 4:0:0, 8x8-transform macroblocks and jmhip_tq_batch).
+//
+// T8: the instantiation for pictures with 8x8-transform macroblocks (luma_transform_size_8x8_flag, mode pad[0]); 4x4-only pictures never select it.
+// In an 8x8-transform macroblock a quad is one 8x8 block: LumaPrediction per 8x8 block (UMV clamp at its origin, macroblock.c:1143), then dct_8x8
+// (transform8x8.c:1452-1653) with the 8-point butterflies across the quad through the block's LDS tile, the quantisation element-wise, the 64-step
+// scan (one list, or CAVLC's four interleaved lists) by the quad's first lane out of the tile; the side record jmhip_mb_residual8 takes the lists.
+__device__ __forceinline__ void wave_lds_sync()       // LDS traffic between lanes of one wave: ordered, nothing more to wait for
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+static_assert(sizeof(jmhip_mb_residual8) % 16 == 0, "side records are copied out of LDS as 16-byte pieces");
+
+template <bool T8>
 __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhip_me_mb *__restrict__ mbs, const jmhip_me_result *__restrict__ me,
                                                         const jmhip_mb_mode *__restrict__ modes_in, jmhip_mb_mode *__restrict__ modes_out,
-                                                        const jmhip_quant *__restrict__ quants, JmMbRes *__restrict__ out, JmMbCoded *__restrict__ coded, int n)
+                                                        const jmhip_quant *__restrict__ quants, JmMbRes *__restrict__ out, JmMbCoded *__restrict__ coded, int n,
+                                                        jmhip_mb_residual8 *__restrict__ out8)
 {
   constexpr int NMB = 4;                               // macroblocks per wave: 16 luma lanes each, then 8 chroma lanes each
   __shared__ __attribute__((aligned(16))) JmMbRes s_rec[NMB];
@@ -680,6 +694,8 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
   __shared__ int s_cost[NMB][JMHIP_NPART];
   __shared__ short s_pos[NMB][2];
   __shared__ __attribute__((aligned(4))) uint8_t s_pc[NMB][2][8][8], s_sc[NMB][2][8][8];      // chroma prediction / source tiles
+  __shared__ int s_t8[T8 ? 4 * NMB : 1][64];                                                 // T8: one coefficient tile per 8x8 block
+  __shared__ __attribute__((aligned(16))) jmhip_mb_residual8 s_rec8[T8 ? NMB : 1];
   const int vb = jm_xcd_item((n + NMB - 1) / NMB);
   if (vb < 0) return;
   // two waves: wave 0 stages and then owns the luma blocks, wave 1 owns chroma (prediction, then dct_chroma) -- the two transform paths run
@@ -700,6 +716,8 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
   if (wv == 0 && tid < NMB && modes_in) m_in = modes_in[mb_of(tid)];
   if (wv == 0 && tid >= 8 && tid < 8 + NMB) { const jmhip_me_mb &mb = mbs[mb_of(tid - 8)]; s_pos[tid - 8][0] = mb.mb_x; s_pos[tid - 8][1] = mb.mb_y; }
   if (wv == 0 && tid >= 16 && tid < 16 + 4 * NMB) { const int hh = (tid - 16) >> 2, k = tid & 3; s_ref[hh][k] = F.blk_ref ? F.blk_ref[(size_t)mb_of(hh) * 4 + k] : mbs[mb_of(hh)].ref; }
+  if constexpr (T8)
+    for (int k = threadIdx.x; k < NMB * (int)(sizeof(jmhip_mb_residual8) / 16); k += 128) reinterpret_cast<uint4 *>(s_rec8)[k] = make_uint4(0, 0, 0, 0);
   __syncthreads();
   if (wv == 0 && tid < NMB) {
     jmhip_mb_mode m;
@@ -766,17 +784,20 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
     const int x4 = 2 * (b8 & 1) + (b4 & 1), y4 = 2 * (b8 >> 1) + (b4 >> 1), bx = 4 * x4, by = 4 * y4;
     const jmhip_quant &q = quants[0];
     const int qp_per = q.qp / 6, q_bits = Q_BITS + qp_per;
+    // an 8x8-transform macroblock predicts per 8x8 block (mc_kernel): the clamp applies to the 8x8 origin, this 4x4 block sits at (ox4, oy4) in it
+    const bool t8 = T8 && s_mode[h].pad[0];
+    const int ox4 = t8 ? 4 * (b4 & 1) : 0, oy4 = t8 ? 4 * (b4 >> 1) : 0;
     int m[4][4], pr[4][4];
     {
       const short *mv = s_mv[h][y4 * 4 + x4];
-      const int bqx = ((mbx * 16 + bx) << 2) + 4 * JMHIP_PAD, bqy = ((mby * 16 + by) << 2) + 4 * JMHIP_PAD;
+      const int bqx = ((mbx * 16 + bx - ox4) << 2) + 4 * JMHIP_PAD, bqy = ((mby * 16 + by - oy4) << 2) + 4 * JMHIP_PAD;
       const int xq = bqx + mv[0], yq = bqy + mv[1], slot = s_ref[h][b8];
       int pdir = 0, slot1 = 0, xq1 = 0, yq1 = 0;                                             // the second list of a B macroblock
       if (F.bi) { const jmhip_mb_bipred &bm = F.bi[mb_of(h)]; pdir = bm.pdir[b8]; slot1 = bm.ref1[b8]; xq1 = bqx + bm.mv1[y4 * 4 + x4][0]; yq1 = bqy + bm.mv1[y4 * 4 + x4][1]; }
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        const uint32_t v0 = pdir != 1 ? luma_row4(F, slot, xq, yq, 0, 0, j) : 0u;
-        const uint32_t v1 = pdir != 0 ? luma_row4(F, slot1, xq1, yq1, 0, 0, j) : 0u;
+        const uint32_t v0 = pdir != 1 ? luma_row4(F, slot, xq, yq, ox4, oy4, j) : 0u;
+        const uint32_t v1 = pdir != 0 ? luma_row4(F, slot1, xq1, yq1, ox4, oy4, j) : 0u;
         const uint32_t sv = *reinterpret_cast<const uint32_t *>(F.cur_y + (size_t)(mby * 16 + by + j) * F.W + mbx * 16 + bx);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -786,51 +807,188 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
         }
       }
     }
-    fwd4(m);
-    int scan_pos = 0, run = -1, nonzero = 0, cost = 0;
-    int fa[4][4];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      constexpr int I0[16] = {0,1,0,0,1,2,3,2,1,0,1,2,3,3,2,3}, J0[16] = {0,0,1,2,1,0,0,1,2,3,3,2,1,2,3,3};
-      constexpr int I1[16] = {0,0,1,0,0,1,1,1,2,2,2,2,3,3,3,3}, J1[16] = {0,1,0,2,3,1,2,3,0,1,2,3,0,1,2,3};
-      const int i0 = I0[k], j0 = J0[k], i1 = I1[k], j1 = J1[k];
-      const int c = q.field_scan ? m[j1][i1] : m[j0][i0];
-      const int idx = q.field_scan ? (j1 * 4 + i1) : (j0 * 4 + i0);
-      run++;
-      const int scaled = iabs(c) * q.levelscale[idx];
-      int level = (scaled + q.leveloffset[idx]) >> q_bits;
-      int deq = 0, fadj = 0;
-      if (level != 0) {
-        if (q.adaptive_rounding) fadj = rsr(q.adapt_rnd_weight * (scaled - (level << q_bits)), q_bits + 1);   // block.c:898
-        nonzero = 1;
-        cost += (level > 1) ? MAXV : c_cost4[q.disthres][run];
-        level = sgnab(level, c);
-        R.lev[blk][scan_pos] = (int16_t)level; R.run[blk][scan_pos] = (uint8_t)run; scan_pos++;
-        deq = rsr((level * q.invlevelscale[idx]) << qp_per, 4);                                             // block.c:907
-        run = -1;
-      }
-      if (q.field_scan) { m[j1][i1] = deq; fa[j1][i1] = fadj; } else { m[j0][i0] = deq; fa[j0][i0] = fadj; }
-    }
-    R.cnt[blk] = (uint8_t)scan_pos;
-    R.coeff_cost[blk] = cost;
-    if (q.adaptive_rounding) {
+    int nonzero = 0, cost = 0;                         // dct_4x4 per lane, or (8x8 transform) the quad's dct_8x8: cost on its first lane, the return value on all four
+    uint32_t rec[4], prd[4];
+    bool done = false;
+    if constexpr (T8) if (t8) {
+      // ---- dct_8x8 (transform8x8.c:1452-1653) on the quad of this 8x8 block, through the block's LDS tile
+      const jmhip_quant &q8 = quants[3];
+      const int qp8 = q8.qp / 6, qb8 = Q_BITS_8 + qp8;
+      const bool interleave = q8.transform8x8_flag && q8.cavlc;                       // transform8x8.c:1502
+      int *T = s_t8[4 * h + b8];
+      jmhip_mb_residual8 &R8 = s_rec8[h];
 #pragma unroll
       for (int j = 0; j < 4; j++)
 #pragma unroll
-        for (int k = 0; k < 4; k++) R.fadj_y[by + j][bx + k] = (int16_t)fa[j][k];
-    }
-    if (scan_pos) inv4(m);
-    uint32_t rec[4], prd[4];
+        for (int k = 0; k < 4; k++) T[(oy4 + j) * 8 + ox4 + k] = m[j][k];
+      wave_lds_sync();
+      // forward8x8 (transform.c:229): rows, then columns; lane b4 of the quad takes rows / columns 2*b4 and 2*b4+1
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-      uint32_t w = 0, pw = 0;
+      for (int rr = 0; rr < 2; rr++) {
+        int p[8], o[8];
+        const int r = 2 * b4 + rr;
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int v = scan_pos ? clip1(q.max_val, rsr(m[j][k], DQ_BITS) + pr[j][k]) : pr[j][k];                // block.c:934 / :942
-        w |= (uint32_t)v << (8 * k); pw |= (uint32_t)pr[j][k] << (8 * k);
+        for (int i = 0; i < 8; i++) p[i] = T[r * 8 + i];
+        fwd8_1d(p, o);
+#pragma unroll
+        for (int i = 0; i < 8; i++) T[r * 8 + i] = o[i];
       }
-      rec[j] = w; prd[j] = pw;
-      *reinterpret_cast<uint32_t *>(&R.recon_y[by + j][bx]) = w;
+      wave_lds_sync();
+#pragma unroll
+      for (int cc = 0; cc < 2; cc++) {
+        int p[8], o[8];
+        const int c = 2 * b4 + cc;
+#pragma unroll
+        for (int j = 0; j < 8; j++) p[j] = T[j * 8 + c];
+        fwd8_1d(p, o);
+#pragma unroll
+        for (int j = 0; j < 8; j++) T[j * 8 + c] = o[j];
+      }
+      wave_lds_sync();
+      // quantisation is element-wise (rows 2*b4, 2*b4+1): the signed level replaces the coefficient; fadjust8x8 beside it
+#pragma unroll
+      for (int rr = 0; rr < 2; rr++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          const int j = 2 * b4 + rr, idx = j * 8 + i, c = T[idx];
+          const int scaled = iabs(c) * q8.levelscale[idx];
+          const int level = (scaled + q8.leveloffset[idx]) >> qb8;
+          if (q8.adaptive_rounding) R.fadj_y[8 * (b8 >> 1) + j][8 * (b8 & 1) + i] = (int16_t)(level ? rsr(q8.adapt_rnd_weight * (scaled - (level << qb8)), qb8 + 1) : 0);
+          T[idx] = level ? sgnab(level, c) : 0;
+        }
+      wave_lds_sync();
+      // the run / level lists are sequential: the quad's first lane walks the 64 scan positions
+      int nz8 = 0;
+      if (b4 == 0) {
+        int run = -1, sp = 0, c8 = 0;
+        int sp4[4] = {0, 0, 0, 0}, run4[4] = {-1, -1, -1, -1};
+        for (int k0 = 0; k0 < 64; k0 += 4) {
+#pragma unroll
+          for (int mc = 0; mc < 4; mc++) {                                             // mc = k & 3: the interleaved list of position k
+            const int k = k0 + mc, i = c_scan8[q8.field_scan][k][0], j = c_scan8[q8.field_scan][k][1];
+            const int lev = T[j * 8 + i];
+            run++; run4[mc]++;
+            if (lev) {
+              nz8 = 1;
+              if (interleave) {
+                c8 += iabs(lev) > 1 ? MAXV : c_cost8[q8.disthres][run4[mc]];
+                R8.lev[b8][16 * mc + sp4[mc]] = (int16_t)lev; R8.run[b8][16 * mc + sp4[mc]] = (uint8_t)run4[mc];
+                sp4[mc]++; run4[mc] = -1;
+              } else {
+                c8 += iabs(lev) > 1 ? MAXV : c_cost8[q8.disthres][run];
+                R8.lev[b8][sp] = (int16_t)lev; R8.run[b8][sp] = (uint8_t)run;
+                sp++; run = -1;
+              }
+            }
+          }
+        }
+        if (interleave) {
+#pragma unroll
+          for (int mc = 0; mc < 4; mc++) R8.cnt[b8][mc] = (uint8_t)sp4[mc];
+        } else R8.cnt[b8][0] = (uint8_t)sp;
+        R8.coeff_cost[b8] = c8; R8.nonzero[b8] = nz8;
+        if (b8 == 0) { R8.transform8x8 = 1; R8.interleaved = interleave ? 1 : 0; }
+        cost = c8;
+      }
+      nz8 = quad_bcast(nz8, 0);
+      nonzero = nz8;
+      wave_lds_sync();
+      // dequantisation (transform8x8.c:1543) and inverse8x8 (transform.c:325) when the block has a level
+#pragma unroll
+      for (int rr = 0; rr < 2; rr++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          const int idx = (2 * b4 + rr) * 8 + i, lev = T[idx];
+          T[idx] = lev ? rsr((lev * q8.invlevelscale[idx]) << qp8, 6) : 0;
+        }
+      if (nz8) {
+        wave_lds_sync();
+#pragma unroll
+        for (int rr = 0; rr < 2; rr++) {
+          int p[8], o[8];
+          const int r = 2 * b4 + rr;
+#pragma unroll
+          for (int i = 0; i < 8; i++) p[i] = T[r * 8 + i];
+          inv8_1d(p, o);
+#pragma unroll
+          for (int i = 0; i < 8; i++) T[r * 8 + i] = o[i];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int cc = 0; cc < 2; cc++) {
+          int p[8], o[8];
+          const int c = 2 * b4 + cc;
+#pragma unroll
+          for (int j = 0; j < 8; j++) p[j] = T[j * 8 + c];
+          inv8_1d(p, o);
+#pragma unroll
+          for (int j = 0; j < 8; j++) T[j * 8 + c] = o[j];
+        }
+      }
+      wave_lds_sync();
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        uint32_t w = 0, pw = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int v = nz8 ? clip1(q8.max_val, rsr(T[(oy4 + j) * 8 + ox4 + k], DQ_BITS) + pr[j][k]) : pr[j][k];
+          w |= (uint32_t)v << (8 * k); pw |= (uint32_t)pr[j][k] << (8 * k);
+        }
+        rec[j] = w; prd[j] = pw;
+        *reinterpret_cast<uint32_t *>(&R.recon_y[by + j][bx]) = w;
+      }
+      // the 4x4 fields of the record are defined as zero for this macroblock
+      reinterpret_cast<uint4 *>(R.lev[blk])[0] = make_uint4(0, 0, 0, 0); reinterpret_cast<uint4 *>(R.lev[blk])[1] = make_uint4(0, 0, 0, 0);
+      reinterpret_cast<uint4 *>(R.run[blk])[0] = make_uint4(0, 0, 0, 0);
+      R.cnt[blk] = 0; R.coeff_cost[blk] = 0;
+      done = true;
+    }
+    if (!done) {
+      fwd4(m);
+      int scan_pos = 0, run = -1;
+      int fa[4][4];
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        constexpr int I0[16] = {0,1,0,0,1,2,3,2,1,0,1,2,3,3,2,3}, J0[16] = {0,0,1,2,1,0,0,1,2,3,3,2,1,2,3,3};
+        constexpr int I1[16] = {0,0,1,0,0,1,1,1,2,2,2,2,3,3,3,3}, J1[16] = {0,1,0,2,3,1,2,3,0,1,2,3,0,1,2,3};
+        const int i0 = I0[k], j0 = J0[k], i1 = I1[k], j1 = J1[k];
+        const int c = q.field_scan ? m[j1][i1] : m[j0][i0];
+        const int idx = q.field_scan ? (j1 * 4 + i1) : (j0 * 4 + i0);
+        run++;
+        const int scaled = iabs(c) * q.levelscale[idx];
+        int level = (scaled + q.leveloffset[idx]) >> q_bits;
+        int deq = 0, fadj = 0;
+        if (level != 0) {
+          if (q.adaptive_rounding) fadj = rsr(q.adapt_rnd_weight * (scaled - (level << q_bits)), q_bits + 1);   // block.c:898
+          nonzero = 1;
+          cost += (level > 1) ? MAXV : c_cost4[q.disthres][run];
+          level = sgnab(level, c);
+          R.lev[blk][scan_pos] = (int16_t)level; R.run[blk][scan_pos] = (uint8_t)run; scan_pos++;
+          deq = rsr((level * q.invlevelscale[idx]) << qp_per, 4);                                             // block.c:907
+          run = -1;
+        }
+        if (q.field_scan) { m[j1][i1] = deq; fa[j1][i1] = fadj; } else { m[j0][i0] = deq; fa[j0][i0] = fadj; }
+      }
+      R.cnt[blk] = (uint8_t)scan_pos;
+      R.coeff_cost[blk] = cost;
+      if (q.adaptive_rounding) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+          for (int k = 0; k < 4; k++) R.fadj_y[by + j][bx + k] = (int16_t)fa[j][k];
+      }
+      if (scan_pos) inv4(m);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        uint32_t w = 0, pw = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int v = scan_pos ? clip1(q.max_val, rsr(m[j][k], DQ_BITS) + pr[j][k]) : pr[j][k];                // block.c:934 / :942
+          w |= (uint32_t)v << (8 * k); pw |= (uint32_t)pr[j][k] << (8 * k);
+        }
+        rec[j] = w; prd[j] = pw;
+        *reinterpret_cast<uint32_t *>(&R.recon_y[by + j][bx]) = w;
+      }
     }
     // ---- _LUMA_COEFF_COST_ per 8x8 block (a quad) and _LUMA_MB_COEFF_COST_ per macroblock: macroblock.c:1236-1258, :1386-1392 (finalize_kernel)
     int cost8 = cost;
@@ -843,7 +1001,7 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
     int bits = (nonzero && keep) ? ((1 << (x4 + 4 * y4)) | (0x10000 << b8)) : 0;      // cbp_blk bit (block_x>>2) + block_y, macroblock.c:1050; cbp bit b8 above it
     bits |= __shfl_xor(bits, 1); bits |= __shfl_xor(bits, 2); bits |= __shfl_xor(bits, 4); bits |= __shfl_xor(bits, 8);
     cbp_blk_luma = bits & 0xffff; cbp_luma = bits >> 16;
-    const unsigned long long nz = __ballot(nonzero != 0);
+    const unsigned long long nz = __ballot(nonzero != 0 && !t8);
     if (l == 0) R.nonzero = (uint16_t)(nz >> (16 * h));
     if (live) {
 #pragma unroll
@@ -989,16 +1147,25 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
     uint4 *dst = reinterpret_cast<uint4 *>(out + i0);
     for (int k = threadIdx.x; k < nlive * (int)(sizeof(JmMbRes) / 16); k += 128) dst[k] = src[k];
   }
+  if constexpr (T8) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(s_rec8);
+    uint4 *dst = reinterpret_cast<uint4 *>(out8 + i0);
+    for (int k = threadIdx.x; k < nlive * (int)(sizeof(jmhip_mb_residual8) / 16); k += 128) dst[k] = src[k];
+  }
 }
 
 }  // namespace
 
 int jm_launch_frame_fused(jmhip_ctx *c, const void *frame_dev, const void *mbs, const void *me, const void *modes_in, void *modes_out,
-                          const void *quants, void *records, void *coded, int n)
+                          const void *quants, void *records, void *coded, int n, void *records8)
 {
   const FrameDev &F = *static_cast<const FrameDev *>(frame_dev);
-  frame_fused_kernel<<<jm_xcd_grid((n + 3) / 4), 128, 0, c->stream>>>(F, (const jmhip_me_mb *)mbs, (const jmhip_me_result *)me, (const jmhip_mb_mode *)modes_in, (jmhip_mb_mode *)modes_out,
-                                                                     (const jmhip_quant *)quants, (JmMbRes *)records, (JmMbCoded *)coded, n);
+  if (records8)
+    frame_fused_kernel<true><<<jm_xcd_grid((n + 3) / 4), 128, 0, c->stream>>>(F, (const jmhip_me_mb *)mbs, (const jmhip_me_result *)me, (const jmhip_mb_mode *)modes_in, (jmhip_mb_mode *)modes_out,
+                                                                           (const jmhip_quant *)quants, (JmMbRes *)records, (JmMbCoded *)coded, n, (jmhip_mb_residual8 *)records8);
+  else
+    frame_fused_kernel<false><<<jm_xcd_grid((n + 3) / 4), 128, 0, c->stream>>>(F, (const jmhip_me_mb *)mbs, (const jmhip_me_result *)me, (const jmhip_mb_mode *)modes_in, (jmhip_mb_mode *)modes_out,
+                                                                            (const jmhip_quant *)quants, (JmMbRes *)records, (JmMbCoded *)coded, n, nullptr);
   if (hipGetLastError() != hipSuccess) return jm_fail(c, JMHIP_ERR_DEVICE, "frame_fused_kernel launch");
   return JMHIP_OK;
 }

@@ -415,7 +415,7 @@ int jmhip_epzs_map_upload(jmhip_ctx *ctx, const int16_t *map, int search_range, 
  * reference slot of every 8x8 block become the inputs of jmhip_residual_frame(modes = NULL), which then runs LumaResidualCoding /
  * ChromaResidualCoding on them (per-8x8 reference pictures: macroblock.c:1009-1110 with SetModesAndRefframe), and of jmhip_deblock_recon.
  * ref_slot: list-0 index -> reference slot, as in the slice calls. */
-int jmhip_slice_to_frame(jmhip_ctx *ctx, const int32_t *ref_slot, int num_refs);     /* reference slots 0..7 */
+int jmhip_slice_to_frame(jmhip_ctx *ctx, const int32_t *ref_slot, int num_refs);     /* any allocated reference slot */
 /* The same for the macroblocks [mb_first, mb_first + mb_count) alone -- a rank of the slice-parallel layout (one slice per GPU,
  * src/slice.c:214 with SliceMode 1) hands ITS slice to the frame stage: job i of jmhip_residual_frame is macroblock mb_first + i, the
  * reconstruction covers those macroblocks' rows (jmhip_recon_pack_band). The range must have been searched in the current picture. */
@@ -550,10 +550,10 @@ int jmhip_residual_frame_q(jmhip_ctx *ctx, const jmhip_mb_mode *modes, const jmh
  * thresholding of src/macroblock.c:1236-1258, :1386-1392 and the chroma cr_cbp. Any output pointer may be NULL. */
 int jmhip_residual_download(jmhip_ctx *ctx, jmhip_tq_result *luma, jmhip_tq_result *chroma, jmhip_mb_mode *modes_out,
                             int32_t *cbp, int64_t *cbp_blk, int n);
-/* The dense per-macroblock record of the fused 4:2:0 frame stage (4x4 transform): what JM's dct_4x4 x16 (src/block.c:843) and dct_chroma x2
+/* The dense per-macroblock record of the fused 4:2:0 frame stage: what JM's dct_4x4 x16 (src/block.c:843) and dct_chroma x2
  * (:1051) leave behind for one macroblock. jmhip_residual_records_download copies the records of the last jmhip_residual_frame as they are
  * (2.4 KB each; jmhip_residual_download expands them into three 5.8 KB jmhip_tq_result) -- the form a slice-level binding answers JM's
- * dct_4x4 / dct_chroma calls from. JMHIP_ERR_UNSUPPORTED when the last frame stage took the separate kernels (4:2:2, 4:0:0, 8x8 transform). */
+ * dct_4x4 / dct_chroma calls from. JMHIP_ERR_UNSUPPORTED when the last frame stage took the separate kernels (4:2:2, 4:0:0, JMHIP_FRAME_FUSED=0). */
 typedef struct jmhip_mb_residual {
   int16_t lev[24][16];           /* (level) lists in scan order: luma blocks 0..15 (JM order b8*4+b4), Cb 16..19, Cr 20..23 (AC) */
   uint8_t run[24][16];
@@ -575,6 +575,23 @@ typedef struct jmhip_mb_residual {
   uint8_t pad2[8];
 } jmhip_mb_residual;
 int jmhip_residual_records_download(jmhip_ctx *ctx, jmhip_mb_residual *records, int n);
+/* 8x8-transform macroblocks (luma_transform_size_8x8_flag, mode pad[0] = 1) of a 4:2:0 picture take the fused stage too. Their luma results
+ * are what dct_8x8 (src/transform8x8.c:1452-1653) leaves behind per 8x8 block, in this side record (832 bytes per macroblock). In the
+ * jmhip_mb_residual of such a macroblock the luma lists, cnt[0..15], coeff_cost and nonzero read 0; recon_y and fadj_y hold the 8x8 path's
+ * reconstruction and fadjust8x8; the chroma fields keep their meaning. jmhip_residual_records8_download copies the side records of the last
+ * jmhip_residual_frame (all zero when it had no 8x8-transform macroblock); JMHIP_ERR_UNSUPPORTED when it took the separate kernels. */
+typedef struct jmhip_mb_residual8 {
+  int16_t lev[4][64];            /* cofAC[b8] levels, scan order. interleaved == 0 (CABAC, or transform8x8_flag off): one list lev[b8][0..cnt[b8][0]-1];
+                                    interleaved == 1 (CAVLC, transform8x8.c:1502): four lists cofAC[b8][k] at lev[b8][16*k .. 16*k+cnt[b8][k]-1] */
+  uint8_t run[4][64];            /* the matching runs; JM's 0 terminator follows each list */
+  uint8_t cnt[4][4];             /* entries of each list (interleaved == 0: cnt[b8][0] only) */
+  int32_t coeff_cost[4];         /* what dct_8x8 adds to *coeff_cost, per 8x8 block */
+  int32_t nonzero[4];            /* dct_8x8's return value per 8x8 block */
+  int32_t transform8x8;          /* the macroblock's luma_transform_size_8x8_flag (0: the rest of the record is 0) */
+  int32_t interleaved;
+  uint8_t pad[8];
+} jmhip_mb_residual8;
+int jmhip_residual_records8_download(jmhip_ctx *ctx, jmhip_mb_residual8 *records, int n);
 /* Keep the prediction picture -- img->mpr of every macroblock of jmhip_residual_frame, luma and chroma (src/macroblock.c:836, :1593) -- beside
  * the recon picture (fused 4:2:0 stage only), and copy it to the host (pel_bytes 1 or 2): a binding that answers JM's LumaPrediction /
  * ChromaPrediction4x4 from the device reads it, and checks its dct inputs against it. */
@@ -641,7 +658,7 @@ int jmhip_ref_unpack_bands(jmhip_ctx *ctx, int ref, const void *chunks_device, i
  * 2 jmhip_quant, 3 jmhip_tq_job, 4 jmhip_tq_result, 5 jmhip_dist_job, 6 jmhip_me_params, 7 jmhip_config,
  * 8 jmhip_mb_mode, 9 jmhip_surface_job, 10 jmhip_bipred_job, 11 jmhip_bipred_result, 12 jmhip_bipred_params, 13 jmhip_predcost_job,
  * 14 jmhip_deblock_mb, 15 jmhip_deblock_blk, 16 jmhip_deblock_params, 17 jmhip_slice_params, 18 jmhip_mb_inter, 19 jmhip_frame_wp,
- * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual. */
+ * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8. */
 int jmhip_sizeof(int which);
 
 /* Flat (no scaling matrix) tables: CalculateQuantParam / CalculateQuant8Param (src/q_matrix.c:451,590) and
