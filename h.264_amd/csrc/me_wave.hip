@@ -32,6 +32,7 @@ struct WaveDev {
   int *prog;                                   // [mbh]: macroblocks finished in the row (x + 1)
   int *flags;                                  // [0] abort (a wait timed out)
   jmhip_mb_inter *out;                         // by macroblock address
+  int *ref8ts;                                 // [nmb][4]: best_ref of the 8x8-transform P8x8 pass per 8x8 block (-1: the pass did not run)
   // EPZS row memories, one stored row per macroblock row of the slice (+ row 0: the state the slice started from): a macroblock reads, per
   // 4x4 column, the row of the macroblock that wrote it last in coding order (state_row) -- which makes any schedule that respects, or
   // iterates towards, the coding order see what JM's single-row arrays would hold
@@ -1943,6 +1944,7 @@ template <int SM> __device__ void macroblock_low(int mbx, int mby, jmhip_mb_inte
     field_set(by0 + (b >> 2), bx0 + (b & 3), r, L.all_mv[b][r][m8][0], L.all_mv[b][r][m8][1]);
     if (threadIdx.x == 0) { out->final_mv[b][0] = L.all_mv[b][r][m8][0]; out->final_mv[b][1] = L.all_mv[b][r][m8][1]; }
   }
+  if (threadIdx.x < 4) D.ref8ts[(size_t)(out - D.out) * 4 + threadIdx.x] = (T8 && any8) ? ref8ts[threadIdx.x] : -1;      // which reference JM's 8x8-transform pass codes
   if (threadIdx.x == 0) {
     out->best_mode = best_mode; out->min_cost = min_cost; out->transform8x8_flag = t8_flag; out->cbp8ts = cbp8ts;
     for (int k = 0; k < 4; k++) { out->b8mode[k] = best_mode == 8 ? b8m[k] : best_mode; out->b8ref[k] = l0ref[best_mode == 8 ? 4 : best_mode][k]; out->p8mode[k] = p8m[k]; out->p8ref[k] = p8r[k]; }
@@ -2304,6 +2306,7 @@ struct SliceState {
   int8_t *ref_idx = nullptr; short *mv = nullptr;
   int *prog = nullptr, *flags = nullptr;
   jmhip_mb_inter *out = nullptr;
+  int *ref8ts = nullptr;                       // [nmb][4] next to out (WaveDev.ref8ts); a slice call rewrites its own macroblocks only
   int *ep_dist = nullptr; short *ep_motion = nullptr; short *ep_col = nullptr;        // row memories: [mbh + 1] stored rows (WaveDev)
   // EPZSMap / EPZSBlkCount: the map (16-bit stamps) and the search counter as the last slice left them (and where the running call writes the
   // next ones), the per-macroblock touch records and the scan's scratch
@@ -2321,13 +2324,14 @@ struct SliceState {
   bool has_col = false;
   int searched_from = 0, searched_to = 0;      // macroblocks [searched_from, searched_to) of the current picture have been searched (by slice calls in order)
   bool t8_any = false;                         // a slice of the current picture was searched with Transform8x8Mode: macroblocks may carry the 8x8-transform flag
+  bool t8_all = false;                         // ... every slice of [searched_from, searched_to) was: ref8ts holds a reference for each of their blocks
 };
 
 }  // namespace
 
 static void slice_state_release(SliceState *s)
 {
-  void *bufs[] = {s->ref_idx, s->mv, s->prog, s->flags, s->out, s->ep_dist, s->ep_motion, s->carry_mb, s->chg[0], s->chg[1], s->memo, s->tie_tab, s->ep_col, s->carry_in, s->carry_out,
+  void *bufs[] = {s->ref_idx, s->mv, s->prog, s->flags, s->out, s->ref8ts, s->ep_dist, s->ep_motion, s->carry_mb, s->chg[0], s->chg[1], s->memo, s->tie_tab, s->ep_col, s->carry_in, s->carry_out,
                   s->carry_slice, s->carry_slice_next, s->um_cost, s->um_cost_snap, s->surf, s->ep_map, s->ep_map_next, s->ep_count, s->ep_count_next, s->ep_first, s->ep_last,
                   s->ep_alias_flag, s->ep_nsearch, s->ep_base, s->ep_seg_last, s->ep_seg_in, s->ep_alias, s->ep_alias_new, s->ep_alias_n};
   for (void *b : bufs) if (b) (void)hipFree(b);
@@ -2342,7 +2346,7 @@ static SliceState *slice_state(jmhip_ctx *c)
   const size_t w4 = c->W / 4, h4 = c->H / 4, nmb = (size_t)c->mbw * c->mbh;
   bool ok = hipMalloc((void **)&s->ref_idx, w4 * h4) == hipSuccess && hipMalloc((void **)&s->mv, w4 * h4 * 4) == hipSuccess &&
             hipMalloc((void **)&s->prog, sizeof(int) * c->mbh) == hipSuccess && hipMalloc((void **)&s->flags, sizeof(int) * 4) == hipSuccess &&
-            hipMalloc((void **)&s->out, sizeof(jmhip_mb_inter) * nmb) == hipSuccess &&
+            hipMalloc((void **)&s->out, sizeof(jmhip_mb_inter) * nmb) == hipSuccess && hipMalloc((void **)&s->ref8ts, sizeof(int) * 4 * nmb) == hipSuccess &&
             hipMalloc((void **)&s->ep_dist, sizeof(int) * (c->mbh + 1) * 7 * w4) == hipSuccess &&
             hipMalloc((void **)&s->ep_motion, sizeof(short) * (c->mbh + 1) * WR * 7 * 4 * w4 * 2) == hipSuccess &&
             hipMalloc((void **)&s->carry_mb, sizeof(short) * nmb * WR * CARRY * 2) == hipSuccess &&
@@ -2352,7 +2356,7 @@ static SliceState *slice_state(jmhip_ctx *c)
             hipMalloc((void **)&s->carry_in, sizeof(short) * c->mbh * WR * CARRY * 2) == hipSuccess && hipMalloc((void **)&s->carry_out, sizeof(short) * c->mbh * WR * CARRY * 2) == hipSuccess &&
             hipMalloc((void **)&s->carry_slice, sizeof(short) * WR * CARRY * 2) == hipSuccess && hipMalloc((void **)&s->carry_slice_next, sizeof(short) * WR * CARRY * 2) == hipSuccess &&
             hipMalloc((void **)&s->um_cost, sizeof(int) * 8 * h4 * w4) == hipSuccess && hipMalloc((void **)&s->um_cost_snap, sizeof(int) * 8 * h4 * w4) == hipSuccess;
-  if (!ok) { slice_state_release(s); return nullptr; }      // nothing half-allocated stays behind: the call fails with NOMEM and may be retried
+  if (!ok || hipMemset(s->ref8ts, 0xff, sizeof(int) * 4 * nmb) != hipSuccess) { slice_state_release(s); return nullptr; }      // nothing half-allocated stays behind: the call fails with NOMEM and may be retried
   c->slice_state = s;
   return s;
 }
@@ -2467,6 +2471,9 @@ extern "C" int jmhip_p_slice_search(jmhip_ctx *c, const jmhip_slice_params *prm,
   // (a new picture's enc_picture->ref_idx / mv need no reset: a macroblock only ever reads entries of macroblocks coded before it, and the
   // previous picture's field is the relaxation schedule's first guess)
   const bool exhaustive = prm->search_mode == JMHIP_SEARCH_FULL || prm->search_mode == JMHIP_SEARCH_FASTFULL;
+  // the slice's entries of the 8x8-transform pass's references: -1 unless a macroblock kernel of this call writes them (the sweeps over the frame
+  // kernels never run that pass); the other slices' entries stay
+  JM_HIP_CHECK(c, hipMemsetAsync(s->ref8ts + (size_t)prm->mb_first * 4, 0xff, sizeof(int) * 4 * (size_t)prm->mb_count, c->stream));
   // schedule: relaxation sweeps over `relax_grid` resident workgroups (default), or JMHIP_SLICE_SCHED=wave: the coding-order wavefront only
   int relax_grid = 0;
   {
@@ -2507,7 +2514,7 @@ extern "C" int jmhip_p_slice_search(jmhip_ctx *c, const jmhip_slice_params *prm,
   D.W = c->W; D.H = c->H; D.Wp = c->Wp; D.Hp = c->Hp; D.mbw = c->mbw; D.mbh = c->mbh; D.w4 = (int)w4; D.h4 = (int)h4;
   D.cur = c->cur_y;
   D.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
-  D.ref_idx = s->ref_idx; D.mv = s->mv; D.prog = s->prog; D.flags = s->flags; D.out = s->out;
+  D.ref_idx = s->ref_idx; D.mv = s->mv; D.prog = s->prog; D.flags = s->flags; D.out = s->out; D.ref8ts = s->ref8ts;
   D.ep_dist = s->ep_dist; D.ep_motion = s->ep_motion; D.ep_col = s->ep_col; D.row0 = row_first;
   D.carry_in = s->carry_in; D.carry_out = s->carry_out; D.um_cost = s->um_cost; D.um_in = s->um_cost_snap; D.carry_mb = s->carry_mb;
   D.n_changed = s->flags + 2;
@@ -2678,8 +2685,8 @@ extern "C" int jmhip_p_slice_search(jmhip_ctx *c, const jmhip_slice_params *prm,
   if (prm->mb_first == 0) s->t8_any = false;
   s->t8_any = s->t8_any || prm->transform8x8_mode != 0;
   // slices in coding order extend the searched range; anything else starts a new one (a rank of the slice-parallel layout searches only its band)
-  if (prm->mb_first != 0 && prm->mb_first == s->searched_to) s->searched_to = prm->mb_first + prm->mb_count;
-  else { s->searched_from = prm->mb_first; s->searched_to = prm->mb_first + prm->mb_count; }
+  if (prm->mb_first != 0 && prm->mb_first == s->searched_to) { s->searched_to = prm->mb_first + prm->mb_count; s->t8_all = s->t8_all && prm->transform8x8_mode != 0; }
+  else { s->searched_from = prm->mb_first; s->searched_to = prm->mb_first + prm->mb_count; s->t8_all = prm->transform8x8_mode != 0; }
   if (results) return jmhip_slice_results_download(c, results, prm->mb_first, prm->mb_count);
   return JMHIP_OK;
 }
@@ -2750,23 +2757,27 @@ namespace {
 // one thread per macroblock: the slice search's record -> the search-stage result layout the frame stage reads (vector per partition: the
 // one of the reference its 8x8 block settled on), the decided mode, the reference slot per 8x8 block
 struct SlotMap { int s[WR]; };
-__global__ void slice_to_frame_kernel(const jmhip_mb_inter *__restrict__ rec, int first, int n, int mbw, SlotMap sm,
-                                      jmhip_me_mb *__restrict__ jobs, jmhip_me_result *__restrict__ res, jmhip_mb_mode *__restrict__ modes, int8_t *__restrict__ blk_ref, int candidates)
+enum { S2F_DECIDED = 0, S2F_CAND = 1, S2F_CAND8 = 2 };   // the decided mode; the P8x8 candidate of the 4x4 transform; that of the 8x8 transform
+__global__ void slice_to_frame_kernel(const jmhip_mb_inter *__restrict__ rec, const int *__restrict__ ref8ts, int first, int n, int mbw, SlotMap sm,
+                                      jmhip_me_mb *__restrict__ jobs, jmhip_me_result *__restrict__ res, jmhip_mb_mode *__restrict__ modes, int8_t *__restrict__ blk_ref, int form)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const jmhip_mb_inter &r = rec[first + i];              // job i of the frame stage = macroblock first + i of the picture
   const int *slots = sm.s;
-  // the decided mode, or (candidates) the P8x8 candidate of submacroblock_mode_decision: its sub-modes and references per 8x8 block
-  const bool p8 = candidates && r.p8mode[0] >= 4;
-  const int32_t *bref = p8 ? r.p8ref : r.b8ref;
+  // the decided mode, or the P8x8 candidate of submacroblock_mode_decision: its sub-modes and references per 8x8 block (4x4 transform), or
+  // sub-mode 4 with the 8x8-transform pass's reference per block (md_low.c:226-251; the host checked that every block has one)
+  const bool p8 = form == S2F_CAND && r.p8mode[0] >= 4, c8 = form == S2F_CAND8;
+  int32_t r8[4];
+  for (int k = 0; k < 4; k++) { const int v = ref8ts[(size_t)(first + i) * 4 + k]; r8[k] = v < 0 ? 0 : v; }
+  const int32_t *bref = c8 ? r8 : p8 ? r.p8ref : r.b8ref;
   jmhip_me_mb &j = jobs[i];
   j.mb_x = (int16_t)((first + i) % mbw); j.mb_y = (int16_t)((first + i) / mbw); j.ref = (int16_t)slots[bref[0]]; j.ref_is_0 = (int16_t)(bref[0] == 0);
   jmhip_me_result &o = res[i];
   for (int p = 0; p < JMHIP_NPART; p++) {
     const PartInfo q = c_part[p];
     const int ref = bref[2 * (q.y4 >> 1) + (q.x4 >> 1)];
-    if (!p8 && r.best_mode == 8 && r.transform8x8_flag && p >= 5 && p < 9) {        // a P8x8 macroblock with the 8x8 transform keeps the vectors of its 8x8-transform pass
+    if ((c8 || (!p8 && r.best_mode == 8 && r.transform8x8_flag)) && p >= 5 && p < 9) {      // a P8x8 macroblock with the 8x8 transform keeps the vectors of its 8x8-transform pass
       const int k = p - 5;
       j.pred_mv[p][0] = r.pred8ts[ref][k][0]; j.pred_mv[p][1] = r.pred8ts[ref][k][1];
       o.mv[p][0] = r.mv8ts[ref][k][0]; o.mv[p][1] = r.mv8ts[ref][k][1]; o.cost[p] = r.cost8ts[ref][k];
@@ -2778,11 +2789,11 @@ __global__ void slice_to_frame_kernel(const jmhip_mb_inter *__restrict__ rec, in
     o.mv_int[p][0] = r.mv_int[ref][p][0]; o.mv_int[p][1] = r.mv_int[ref][p][1]; o.cost_int[p] = r.cost_int[ref][p];
   }
   jmhip_mb_mode m;
-  m.mode = (int8_t)(p8 ? 8 : r.best_mode);
+  m.mode = (int8_t)(p8 || c8 ? 8 : r.best_mode);
   // (P skip is not a mode of the rdopt = 0 decision: md_low.c:655 turns a 16x16 macroblock into a skip AFTER residual coding, when cbp == 0,
   // ref_idx == 0 and the vector equals skip_mv -- the caller has all three)
-  for (int k = 0; k < 4; k++) { m.b8mode[k] = (int8_t)(p8 ? r.p8mode[k] : (r.best_mode == 8 ? r.b8mode[k] : 4)); blk_ref[(size_t)i * 4 + k] = (int8_t)slots[bref[k]]; }
-  m.pad[0] = (int8_t)(!p8 && r.transform8x8_flag ? 1 : 0);      // luma_transform_size_8x8_flag as the decision left it (the residual coder's transform)
+  for (int k = 0; k < 4; k++) { m.b8mode[k] = (int8_t)(c8 ? 4 : p8 ? r.p8mode[k] : (r.best_mode == 8 ? r.b8mode[k] : 4)); blk_ref[(size_t)i * 4 + k] = (int8_t)slots[bref[k]]; }
+  m.pad[0] = (int8_t)(c8 || (!p8 && r.transform8x8_flag) ? 1 : 0);      // luma_transform_size_8x8_flag as the decision left it (the residual coder's transform)
   m.pad[1] = m.pad[2] = 0;
   modes[i] = m;
 }
@@ -2794,10 +2805,11 @@ extern "C" int jmhip_slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int n
   return jmhip_slice_to_frame_band(c, ref_slot, num_refs, 0, c->mbw * c->mbh);
 }
 
-static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count, int candidates);
-extern "C" int jmhip_slice_to_frame_band(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count) { return slice_to_frame(c, ref_slot, num_refs, mb_first, mb_count, 0); }
-extern "C" int jmhip_slice_to_frame_candidates(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count) { return slice_to_frame(c, ref_slot, num_refs, mb_first, mb_count, 1); }
-static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count, int candidates)
+static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count, int form);
+extern "C" int jmhip_slice_to_frame_band(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count) { return slice_to_frame(c, ref_slot, num_refs, mb_first, mb_count, S2F_DECIDED); }
+extern "C" int jmhip_slice_to_frame_candidates(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count) { return slice_to_frame(c, ref_slot, num_refs, mb_first, mb_count, S2F_CAND); }
+extern "C" int jmhip_slice_to_frame_candidates8(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count) { return slice_to_frame(c, ref_slot, num_refs, mb_first, mb_count, S2F_CAND8); }
+static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count, int form)
 {
   if (!c || !ref_slot || num_refs < 1 || num_refs > JMHIP_SLICE_REFS) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame: arguments") : JMHIP_ERR_ARG;
   if (!c->slice_state) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame: no slice has been searched");
@@ -2805,6 +2817,7 @@ static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, i
   const int n = mb_count;
   if (mb_first < 0 || mb_count < 1 || mb_first + mb_count > c->mbw * c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame: macroblock range outside the picture");
   if (mb_first < s->searched_from || mb_first + mb_count > s->searched_to) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame: not every macroblock of the range has been searched in the current picture (slices must cover it in order)");
+  if (form == S2F_CAND8 && !s->t8_all) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_to_frame_candidates8: the searched slices did not use Transform8x8Mode (no 8x8-transform P8x8 pass)");
   unsigned mask = 0;
   SlotMap sm{};
   for (int r = 0; r < num_refs; r++) {
@@ -2825,13 +2838,23 @@ static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, i
       if (dev >= 0 && dev < 64) part_uploaded[dev] = true;
     }
   }
-  slice_to_frame_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(s->out, mb_first, n, c->mbw, sm, (jmhip_me_mb *)c->me_jobs_dev,
-                                                                (jmhip_me_result *)c->me_res_dev, (jmhip_mb_mode *)c->fr_modes + n, (int8_t *)c->fr_blk_ref, candidates);
+  slice_to_frame_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(s->out, s->ref8ts, mb_first, n, c->mbw, sm, (jmhip_me_mb *)c->me_jobs_dev,
+                                                                (jmhip_me_result *)c->me_res_dev, (jmhip_mb_mode *)c->fr_modes + n, (int8_t *)c->fr_blk_ref, form);
   JM_HIP_CHECK(c, hipGetLastError());
   // the search-stage arrays now hold this picture; a resident re-run of jmhip_me_frame on them is meaningless and is refused (geometry check)
   c->me_n = n; c->me_ref_mask = mask; c->me_last_mode = 0x7fffffff; c->me_fast_idx.clear(); c->me_gen_idx.clear();
   c->fr_from_slices = true;
-  c->fr_slices_t8 = s->t8_any && !candidates;      // (the candidates are coded with the 4x4 transform: the P8x8 pass of the 4x4 transform)
+  c->fr_slices_t8 = s->t8_any && form != S2F_CAND;      // (the 4x4-transform candidates are coded with the 4x4 transform, the 8x8-transform ones with the 8x8)
+  return JMHIP_OK;
+}
+
+extern "C" int jmhip_slice_ref8ts_download(jmhip_ctx *c, int32_t *ref8ts, int mb_first, int mb_count)
+{
+  if (!c || !ref8ts || mb_first < 0 || mb_count < 1 || mb_first + mb_count > c->mbw * c->mbh || !c->slice_state) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_ref8ts_download: arguments") : JMHIP_ERR_ARG;
+  SliceState *s = static_cast<SliceState *>(c->slice_state);
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  JM_HIP_CHECK(c, hipMemcpyAsync(ref8ts, s->ref8ts + (size_t)mb_first * 4, sizeof(int32_t) * 4 * (size_t)mb_count, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
 

@@ -231,6 +231,8 @@ def load_library():
     lib.jmhip_slice_to_frame.argtypes = [vp, vp, ip]
     lib.jmhip_slice_to_frame_band.argtypes = [vp, vp, ip, ip, ip]
     lib.jmhip_slice_to_frame_candidates.argtypes = [vp, vp, ip, ip, ip]
+    lib.jmhip_slice_to_frame_candidates8.argtypes = [vp, vp, ip, ip, ip]
+    lib.jmhip_slice_ref8ts_download.argtypes = [vp, vp, ip, ip]
     lib.jmhip_frame_wp_set.argtypes = [vp, vp]
     lib.jmhip_frame_bipred_set.argtypes = [vp, vp, ip, vp]
     for which, dt in ((0, ME_MB_DTYPE), (1, ME_RESULT_DTYPE), (2, QUANT_DTYPE), (3, TQ_JOB_DTYPE), (4, TQ_RESULT_DTYPE),
@@ -445,6 +447,17 @@ class Context:
         """The same for macroblocks [mb_first, mb_first + mb_count) alone (a rank's slice): job i of residual_frame is macroblock mb_first + i."""
         a = np.ascontiguousarray(ref_slot, dtype=np.int32)
         self._chk(self.lib.jmhip_slice_to_frame_candidates(self.h, _ptr(a), len(a), mb_first, mb_count), "jmhip_slice_to_frame_candidates")
+
+    def slice_to_frame_candidates8(self, ref_slot, mb_first, mb_count):
+        """Every macroblock of the range in its 8x8-transform P8x8 candidate form (sub-mode 4, the 8x8 transform, slice_ref8ts per block)."""
+        a = np.ascontiguousarray(ref_slot, dtype=np.int32)
+        self._chk(self.lib.jmhip_slice_to_frame_candidates8(self.h, _ptr(a), len(a), mb_first, mb_count), "jmhip_slice_to_frame_candidates8")
+
+    def slice_ref8ts(self, mb_first, mb_count):
+        """(mb_count, 4) int32: the reference index of the 8x8-transform P8x8 pass per 8x8 block (-1 where that pass did not run)."""
+        out = np.zeros((mb_count, 4), np.int32)
+        self._chk(self.lib.jmhip_slice_ref8ts_download(self.h, _ptr(out), mb_first, mb_count), "jmhip_slice_ref8ts_download")
+        return out
 
     def frame_wp_set(self, wp=None):
         """wp: None (off) or dict(luma_round, luma_denom, chroma_round, chroma_denom, weight[(slot, comp)], offset[(slot, comp)] as (16,3) arrays)."""

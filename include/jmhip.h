@@ -424,6 +424,16 @@ int jmhip_slice_to_frame_band(jmhip_ctx *ctx, const int32_t *ref_slot, int num_r
  * decided mode: jmhip_residual_frame then yields what LumaResidualCoding8x8 computes for the candidate inside submacroblock_mode_decision
  * (src/mode_decision.c:874). The reconstruction of that pass is not a picture: call it BEFORE the hand-over of the decision. */
 int jmhip_slice_to_frame_candidates(jmhip_ctx *ctx, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count);
+/* ... or in the 8x8-transform P8x8 candidate form, the pass JM runs first when Transform8x8Mode is set (src/md_low.c:226-251): sub-mode 4 in every
+ * 8x8 block, luma_transform_size_8x8_flag = 1, the block's reference of that pass (jmhip_slice_ref8ts_download) and its vectors (mv8ts / pred8ts /
+ * cost8ts ...). jmhip_residual_frame then yields what LumaResidualCoding8x8 (src/macroblock.c:1143-1185) computes inside
+ * submacroblock_mode_decision(..., transform8x8 = 1); it needs quants[3]. JMHIP_ERR_ARG if the searched slices of the range did not use
+ * Transform8x8Mode. Like the other candidate form, call it BEFORE the hand-over of the decision. */
+int jmhip_slice_to_frame_candidates8(jmhip_ctx *ctx, const int32_t *ref_slot, int num_refs, int mb_first, int mb_count);
+/* The reference index (into the slice's list 0) each 8x8 block settled on in the 8x8-transform P8x8 pass -- best_ref of list0_cost in
+ * submacroblock_mode_decision, src/mode_decision.c:255 --, host array [mb_count][4]; -1 where that pass did not run (Transform8x8Mode 0, no 8x8
+ * partition enabled). jmhip_mb_inter keeps it only where the decision is that pass (b8ref). A slice search rewrites its own macroblocks' entries. */
+int jmhip_slice_ref8ts_download(jmhip_ctx *ctx, int32_t *ref8ts, int mb_first, int mb_count);
 
 /* ------------------------------------------------------------------ low-complexity (rdopt off) mode-decision costs */
 

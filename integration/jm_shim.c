@@ -27,6 +27,10 @@
  *        prediction picture and the per-macroblock records -- a prediction call after checking that JM asks for the block the device decided
  *        (mode, reference, vectors), a dct call after checking that JM's img->mpr / img->m7 are the prediction and residual the device used
  *        (anything else is a fatal error).
+ * 0x10000 (with 0x4000) the frame stage at slice level also with Transform8x8Mode 1 / 2 (opt-in: not part of the default mask). The device codes up to
+ *        three passes per slice in JM's order -- the 8x8-transform P8x8 candidate (src/md_low.c:226-251, jmhip_slice_to_frame_candidates8), the
+ *        4x4-transform P8x8 candidate (:254-273, Transform8x8Mode 1 only) and the decision -- and dct_8x8 calls are answered from the 8x8 lists
+ *        (jmhip_mb_residual8) of the pass whose prediction JM works on, with the same checks as dct_4x4.
  * 0x8000 the sub-pel planes stay on the device until JM is about to read them: getSubImagesLuma / getSubImagesChroma still upload the finished picture
  *        and build the planes, but only the integer plane (which JM's weighted-prediction estimation reads) crosses back at once; the other planes
  *        of a picture are fetched into JM's rows the first time a call is FORWARDED to JM code that reads reference planes (JM's own
@@ -63,13 +67,14 @@ extern const int LEVELMVLIMIT[17][6];
 extern int *mvbits;                       /* src/mv-search.c:59 */
 
 enum { S_LUMA, S_CHROMA, S_FULL, S_SUB, S_FAST, S_D4, S_D8, S_D16, S_DCR, S_WALK, S_SAD, S_SATD, S_BIFULL, S_BISUB, S_TDEC, S_SKIPC, S_BIDC, S_DEBLOCK, S_SLICE, S_BMS,
-       S_FRAME, S_D4R, S_DCRR, S_LPRED, S_CPRED, S_LAZY, S_COUNT };
+       S_FRAME, S_D4R, S_DCRR, S_LPRED, S_CPRED, S_LAZY, S_D8R, S_LPREDC, S_COUNT };
 static const char *s_names[S_COUNT] = { "getSubImagesLuma", "getSubImagesChroma", "FullPelBlockMotionSearch",
   "SubPelBlockMotionSearch", "FastFullPelBlockMotionSearch", "dct_4x4", "dct_8x8", "dct_16x16", "dct_chroma",
   "EPZS_UMHex_integer_walks", "computeSAD", "computeSATD", "FullPelBlockMotionBiPred", "SubPelBlockSearchBiPred",
   "TransformDecision", "GetSkipCostMB", "BIDPartitionCost", "DeblockFrame",
   "P slices (one device call each)", "BlockMotionSearch",
-  "frame stage of P slices", "dct_4x4 (slice records)", "dct_chroma (slice records)", "LumaPrediction (slice)", "ChromaPrediction4x4 (slice)", "sub-pel planes fetched on demand" };
+  "frame stage of P slices", "dct_4x4 (slice records)", "dct_chroma (slice records)", "LumaPrediction (slice)", "ChromaPrediction4x4 (slice)", "sub-pel planes fetched on demand",
+  "dct_8x8 (slice records)", "LumaPrediction (mode decision costs)" };
 static long n_dev[S_COUNT], n_fwd[S_COUNT];
 static double t_dev[S_COUNT], t_last[S_COUNT];             /* JMHIP_SHIM_STATS: wall seconds inside the coarse device-side hooks (planes, slice search, loop filter) */
 static int stats_on;
@@ -736,6 +741,10 @@ extern void SetModesAndRefframe(Macroblock *currMB, int b8, short *p_dir, int *l
 extern void LumaPrediction(Macroblock *currMB, int block_x, int block_y, int block_size_x, int block_size_y, int p_dir, int l0_mode,
                            int l1_mode, short l0_ref_idx, short l1_ref_idx);
 
+/* > 0 while TransformDecision / GetSkipCostMB run: their LumaPrediction calls form distortions of the mode decision, not the prediction of a
+   transform call -- JM computes them (counted apart from the frame stage's LumaPrediction calls) */
+static int fr_cost_scope;
+
 /* one job from JM's state: per 4x4 block the list-0 vector of its mode and the slot of its reference; 0 if the device cannot take it
  * (bi-pred / list 1 / direct blocks, weighted prediction, field pictures, SSE) */
 static int predcost_job(Macroblock *currMB, jmhip_predcost_job *job, int skip)
@@ -768,19 +777,23 @@ int TransformDecision(Macroblock *currMB, int block_check, int *cost)
   static int (*orig)(Macroblock *, int, int *);
   jmhip_predcost_job job; int32_t out[1][2];
   if (!(shim_mask & 0x400) || block_check != -1 || !predcost_job(currMB, &job, 0)) {
+    int r;
     if (!orig) orig = next_sym("TransformDecision");
     n_fwd[S_TDEC]++;
-    return orig(currMB, block_check, cost);
+    fr_cost_scope++; r = orig(currMB, block_check, cost); fr_cost_scope--;
+    return r;
   }
   OK(jmhip_pred_cost_batch(g, &job, 1, input->ModeDecisionMetric, JMHIP_DIFF64_SEQUENTIAL, out));
   {
     /* JM leaves the macroblock's prediction in img->mpr (later code may read it): keep that side effect with JM's own routine */
     int b8, bx, by, l0_mode, l1_mode; short p_dir, l0_ref, l1_ref;
+    fr_cost_scope++;
     for (b8 = 0; b8 < 4; b8++) {
       SetModesAndRefframe(currMB, b8, &p_dir, &l0_mode, &l1_mode, &l0_ref, &l1_ref);
       for (by = (b8 >> 1) << 3; by < ((b8 >> 1) << 3) + 8; by += 4)
         for (bx = (b8 & 1) << 3; bx < ((b8 & 1) << 3) + 8; bx += 4) LumaPrediction(currMB, bx, by, 4, 4, p_dir, l0_mode, l1_mode, l0_ref, l1_ref);
     }
+    fr_cost_scope--;
   }
   n_dev[S_TDEC]++;
   if (input->Transform8x8Mode == 2) return 1;          /* macroblock.c:1508-1517 */
@@ -794,12 +807,14 @@ int GetSkipCostMB(Macroblock *currMB)
   static int (*orig)(Macroblock *);
   jmhip_predcost_job job; int32_t out[1][2];
   if (!(shim_mask & 0x400) || !predcost_job(currMB, &job, 1)) {
+    int r;
     if (!orig) orig = next_sym("GetSkipCostMB");
     n_fwd[S_SKIPC]++;
-    return orig(currMB);
+    fr_cost_scope++; r = orig(currMB); fr_cost_scope--;
+    return r;
   }
   OK(jmhip_pred_cost_batch(g, &job, 1, input->ModeDecisionMetric, JMHIP_DIFF64_RASTER, out));
-  { int bx, by; for (by = 0; by < 16; by += 4) for (bx = 0; bx < 16; bx += 4) LumaPrediction(currMB, bx, by, 4, 4, 0, 0, 0, 0, 0); }   /* img->mpr side effect */
+  { int bx, by; fr_cost_scope++; for (by = 0; by < 16; by += 4) for (bx = 0; bx < 16; bx += 4) LumaPrediction(currMB, bx, by, 4, 4, 0, 0, 0, 0, 0); fr_cost_scope--; }   /* img->mpr side effect */
   n_dev[S_SKIPC]++;
   return (input->rdopt == 0 && input->Transform8x8Mode) ? out[0][1] : out[0][0];      /* mv-search.c:1167-1177 */
 }
@@ -893,6 +908,7 @@ static void put_list(int *lev_dst, int *run_dst, const int32_t *lev, const int32
 }
 
 static int fr_dct4(Macroblock *currMB, int block_x, int block_y, int *coeff_cost, int *ret);
+static int fr_dct8(Macroblock *currMB, int b8, int *coeff_cost, int *ret);
 static int fr_dctc(Macroblock *currMB, int uv, int cr_cbp, int *ret);
 
 int dct_4x4(Macroblock *currMB, ColorPlane pl, int block_x, int block_y, int *coeff_cost, int intra)
@@ -934,6 +950,7 @@ int dct_8x8(Macroblock *currMB, ColorPlane pl, int b8, int *coeff_cost, int intr
   static int (*orig)(Macroblock *, ColorPlane, int, int *, int);
   static jmhip_tq_job job; static jmhip_tq_result res; static jmhip_quant q;
   int block_x = 8 * (b8 & 1), block_y = 8 * (b8 >> 1);
+  { int r; if (pl == 0 && !intra && fr_dct8(currMB, b8, coeff_cost, &r)) return r; }
   int ok = (shim_mask & 0x20) && ctx_ready() && !(currMB->qp_scaled[pl] == 0 && img->lossless_qpprime_flag == 1) &&
            img->type != SP_SLICE;
   if (ok) ok = fill_tiles(&job, img->m7[pl], img->mpr[pl], block_x, block_y, 8, 8);
@@ -1074,15 +1091,19 @@ static struct {
   /* ... and the same for the P8x8 CANDIDATE of every macroblock, which JM predicts and transforms per 8x8 block inside submacroblock_mode_decision
      (src/mode_decision.c:874) before it decides: luma only (jmhip_slice_to_frame_candidates) */
   jmhip_mb_residual *rec2; int cap2; imgpel *pred2; int have2;
+  /* Transform8x8Mode (mask 0x10000): the side records of the decision (rec8), and the 8x8-transform P8x8 candidate that JM codes first
+     (src/md_low.c:226-251) with the reference per 8x8 block that pass settled on (ref8ts) */
+  int t8; jmhip_mb_residual8 *rec8; int cap8;
+  jmhip_mb_residual *rec3; jmhip_mb_residual8 *rec83; int32_t *ref8ts; int cap3; imgpel *pred3; int have3;
   /* JM also predicts and transforms blocks the decision then discards (the P8x8 candidate of every macroblock, src/mode_decision.c:874): a dct call
      is answered from the record only when the prediction it works on was -- per macroblock, the luma 4x4 blocks / chroma 4x4 blocks whose LAST
      prediction call asked for the decided block and was answered from the prediction picture */
-  int ok_mb; unsigned long ok_serial; unsigned ok_luma, ok_luma2, ok_chroma[2];      /* ok_luma2: ... was answered from the candidate's prediction picture */
+  int ok_mb; unsigned long ok_serial; unsigned ok_luma, ok_luma2, ok_luma3, ok_chroma[2];      /* ok_luma2 / ok_luma3: ... the 4x4- / 8x8-transform candidate's */
 } fr;
 
 static void fr_ok_mb(void)
 {
-  if (fr.ok_mb != img->current_mb_nr || fr.ok_serial != pic_serial) { fr.ok_mb = img->current_mb_nr; fr.ok_serial = pic_serial; fr.ok_luma = fr.ok_luma2 = 0; fr.ok_chroma[0] = fr.ok_chroma[1] = 0; }
+  if (fr.ok_mb != img->current_mb_nr || fr.ok_serial != pic_serial) { fr.ok_mb = img->current_mb_nr; fr.ok_serial = pic_serial; fr.ok_luma = fr.ok_luma2 = fr.ok_luma3 = 0; fr.ok_chroma[0] = fr.ok_chroma[1] = 0; }
 }
 static unsigned fr_luma_bits(int block_x, int block_y, int bsx, int bsy)
 {
@@ -1107,15 +1128,17 @@ static void fr_diverged(const char *what, int x, int y)
 /* right after the slice search: prediction, residual, transform, quantisation and reconstruction of the slice's macroblocks on the device */
 static void fr_run(const jmhip_slice_params *p, int first, int count)
 {
-  static jmhip_quant q[3];
+  static jmhip_quant q[4];
   jmhip_quant qv;
   jmhip_frame_wp wp;
   Macroblock *mb = &img->mb_data[first];
   const int qp = mb->qp_scaled[0], qc0 = mb->qpc[0] + img->bitdepth_chroma_qp_scale, qc1 = mb->qpc[1] + img->bitdepth_chroma_qp_scale;
+  const int t8 = input->Transform8x8Mode, nq = t8 ? 4 : 3;
+  const int p8 = input->InterSearch[0][4] || input->InterSearch[0][5] || input->InterSearch[0][6] || input->InterSearch[0][7];      /* enc_mb.valid[P8x8] */
   const double t0 = now_s();
   int r, c;
   fr.active = 0;
-  if (!(shim_mask & 0x4000) || sl.spec || img->yuv_format != YUV420 || input->Transform8x8Mode || img->type != P_SLICE || img->NoResidueDirect ||
+  if (!(shim_mask & 0x4000) || sl.spec || img->yuv_format != YUV420 || (t8 && !(shim_mask & 0x10000)) || img->type != P_SLICE || img->NoResidueDirect ||
       (qp == 0 && img->lossless_qpprime_flag == 1) || mb->is_field_mode) return;
   for (r = 0; r < p->num_refs; r++) if (p->ref_slot[r] >= 8 && !slots[p->ref_slot[r]].has_chroma) return;      /* chroma samples are computed from reference slots 0..7 only */
   /* the inter quantisers of the slice (no rate control, no macroblock-level dquant: one qp); Cb and Cr must share theirs */
@@ -1123,7 +1146,12 @@ static void fr_run(const jmhip_slice_params *p, int first, int count)
   fill_quant(&q[1], qc0, LevelScale4x4Comp[1][0][qp_rem_matrix[qc0]], InvLevelScale4x4Comp[1][0][qp_rem_matrix[qc0]], LevelOffset4x4Comp[1][0][qc0], 4, mb, AdaptRndCrWeight, img->max_imgpel_value_comp[1]);
   fill_quant(&qv, qc1, LevelScale4x4Comp[2][0][qp_rem_matrix[qc1]], InvLevelScale4x4Comp[2][0][qp_rem_matrix[qc1]], LevelOffset4x4Comp[2][0][qc1], 4, mb, AdaptRndCrWeight, img->max_imgpel_value_comp[2]);
   if (memcmp(&q[1], &qv, sizeof(qv))) return;
+  q[0].transform8x8_flag = q[1].transform8x8_flag = 0;
   q[2] = q[1];
+  if (t8) {                  /* the inter 8x8 luma quantiser, as dct_8x8 fills it (transform8x8.c:1482-1489) for a macroblock with the 8x8 transform */
+    fill_quant(&q[3], qp, LevelScale8x8Comp[0][0][qp_rem_matrix[qp]], InvLevelScale8x8Comp[0][0][qp_rem_matrix[qp]], LevelOffset8x8Comp[0][0][qp], 8, mb, AdaptRndWeight, img->max_imgpel_value);
+    q[3].transform8x8_flag = 1;
+  }
   memset(&wp, 0, sizeof(wp));
   if (active_pps->weighted_pred_flag) {
     wp.enable = 1; wp.luma_round = wp_luma_round; wp.luma_denom = luma_log_weight_denom; wp.chroma_round = wp_chroma_round; wp.chroma_denom = chroma_log_weight_denom;
@@ -1131,11 +1159,28 @@ static void fr_run(const jmhip_slice_params *p, int first, int count)
   }
   OK(jmhip_frame_wp_set(g, &wp));
   OK(jmhip_frame_keep_prediction(g, 1));
-  fr.have2 = 0;
-  if (input->InterSearch[0][4] || input->InterSearch[0][5] || input->InterSearch[0][6] || input->InterSearch[0][7]) {
-    /* first the P8x8 candidates (their reconstruction is not a picture: the decision's pass below overwrites it) */
+  fr.have2 = fr.have3 = 0; fr.t8 = t8 != 0;
+  if (t8 && p8) {
+    /* JM's first pass (md_low.c:226-251): the 8x8-transform P8x8 candidate, sub-mode 4 with each block's reference of that pass */
+    if (fr.cap3 < count) {
+      free(fr.rec3); free(fr.rec83); free(fr.ref8ts);
+      fr.rec3 = malloc(sizeof(jmhip_mb_residual) * (size_t)count); fr.rec83 = malloc(sizeof(jmhip_mb_residual8) * (size_t)count); fr.ref8ts = malloc(sizeof(int32_t) * 4 * (size_t)count);
+      fr.cap3 = count;
+    }
+    if (!fr.pred3) fr.pred3 = malloc(sizeof(imgpel) * (size_t)g_w * g_h);
+    if (!fr.rec3 || !fr.rec83 || !fr.ref8ts || !fr.pred3) { fprintf(stderr, "jm_shim: out of memory\n"); exit(96); }
+    OK(jmhip_slice_ref8ts_download(g, fr.ref8ts, first, count));
+    OK(jmhip_slice_to_frame_candidates8(g, p->ref_slot, p->num_refs, first, count));
+    OK(jmhip_residual_frame_q(g, NULL, q, 4));
+    OK(jmhip_residual_records_download(g, fr.rec3, count));
+    OK(jmhip_residual_records8_download(g, fr.rec83, count));
+    OK(jmhip_pred_download(g, fr.pred3, NULL, NULL, (int)sizeof(imgpel)));
+    fr.have3 = 1;
+  }
+  if (p8 && t8 != 2) {
+    /* the P8x8 candidates of the 4x4 transform (their reconstruction is not a picture: the decision's pass below overwrites it) */
     OK(jmhip_slice_to_frame_candidates(g, p->ref_slot, p->num_refs, first, count));
-    OK(jmhip_residual_frame(g, NULL, q));
+    OK(jmhip_residual_frame_q(g, NULL, q, nq));
     if (fr.cap2 < count) { free(fr.rec2); fr.rec2 = malloc(sizeof(jmhip_mb_residual) * (size_t)count); fr.cap2 = count; }
     if (!fr.pred2) fr.pred2 = malloc(sizeof(imgpel) * (size_t)g_w * g_h);
     if (!fr.rec2 || !fr.pred2) { fprintf(stderr, "jm_shim: out of memory\n"); exit(96); }
@@ -1144,14 +1189,16 @@ static void fr_run(const jmhip_slice_params *p, int first, int count)
     fr.have2 = 1;
   }
   OK(jmhip_slice_to_frame_band(g, p->ref_slot, p->num_refs, first, count));
-  OK(jmhip_residual_frame(g, NULL, q));
+  OK(jmhip_residual_frame_q(g, NULL, q, nq));
   if (fr.cap < count) { free(fr.rec); fr.rec = malloc(sizeof(jmhip_mb_residual) * (size_t)count); fr.cap = count; }
+  if (t8 && fr.cap8 < count) { free(fr.rec8); fr.rec8 = malloc(sizeof(jmhip_mb_residual8) * (size_t)count); fr.cap8 = count; }
   if (!fr.pred_ready) {
     fr.pred[0] = malloc(sizeof(imgpel) * (size_t)g_w * g_h); fr.pred[1] = malloc(sizeof(imgpel) * (size_t)(g_w / 2) * (g_h / 2)); fr.pred[2] = malloc(sizeof(imgpel) * (size_t)(g_w / 2) * (g_h / 2));
     fr.pred_ready = 1;
   }
-  if (!fr.rec || !fr.pred[0] || !fr.pred[1] || !fr.pred[2]) { fprintf(stderr, "jm_shim: out of memory\n"); exit(96); }
+  if (!fr.rec || (t8 && !fr.rec8) || !fr.pred[0] || !fr.pred[1] || !fr.pred[2]) { fprintf(stderr, "jm_shim: out of memory\n"); exit(96); }
   OK(jmhip_residual_records_download(g, fr.rec, count));
+  if (t8) OK(jmhip_residual_records8_download(g, fr.rec8, count));
   OK(jmhip_pred_download(g, fr.pred[0], fr.pred[1], fr.pred[2], (int)sizeof(imgpel)));
   fr.active = 1; fr.serial = pic_serial; fr.mb_first = first; fr.mb_count = count;
   n_dev[S_FRAME]++; t_last[S_FRAME] = now_s() - t0; t_dev[S_FRAME] += t_last[S_FRAME];
@@ -1193,30 +1240,56 @@ static int fr_asks_candidate(int bx0, int by0, int bx1, int by1, int p_dir, int 
   return 1;
 }
 
+/* ... or for the 8x8-transform P8x8 candidate's (sub-mode 4, the reference that pass settled on for the 8x8 block, its vector of that pass)? */
+static int fr_asks_candidate8(int bx0, int by0, int bx1, int by1, int p_dir, int l0_mode, short l0_ref)
+{
+  const jmhip_mb_inter *d = &sl.rec[img->current_mb_nr - sl.mb_first];
+  const int32_t *ref8 = fr.ref8ts + (size_t)(img->current_mb_nr - fr.mb_first) * 4;
+  int bx, by;
+  if (!fr.have3 || p_dir != 0 || l0_ref < 0 || l0_ref >= JMHIP_SLICE_REFS || l0_mode != 4) return 0;
+  for (by = by0; by < by1; by++) for (bx = bx0; bx < bx1; bx++) {
+    const int b8 = 2 * (by >> 1) + (bx >> 1);
+    const short *v = img->all_mv[by][bx][LIST_0][l0_ref][4];
+    if (l0_ref != ref8[b8] || v[0] != d->mv8ts[l0_ref][b8][0] || v[1] != d->mv8ts[l0_ref][b8][1]) return 0;
+  }
+  return 1;
+}
+
+/* does the block of a pass's prediction picture hold the samples img->mpr[0] now holds? */
+static int fr_same_pred(const imgpel *pic, int block_x, int block_y, int bsx, int bsy)
+{
+  int j;
+  for (j = block_y; j < block_y + bsy; j++)
+    if (memcmp(&img->mpr[0][j][block_x], pic + (size_t)(img->pix_y + j) * g_w + img->pix_x + block_x, sizeof(imgpel) * (size_t)bsx)) return 0;
+  return 1;
+}
+
 void LumaPrediction(Macroblock *currMB, int block_x, int block_y, int block_size_x, int block_size_y, int p_dir, int l0_mode, int l1_mode, short l0_ref_idx, short l1_ref_idx)
 {
   static void (*orig)(Macroblock *, int, int, int, int, int, int, int, short, short);
-  if (fr_rec_cur()) { fr_ok_mb(); fr.ok_luma &= ~fr_luma_bits(block_x, block_y, block_size_x, block_size_y); fr.ok_luma2 &= ~fr_luma_bits(block_x, block_y, block_size_x, block_size_y); }
-  if (fr_rec_cur() && sl.active && fr_asks_decided(block_x >> 2, block_y >> 2, (block_x + block_size_x) >> 2, (block_y + block_size_y) >> 2, p_dir, l0_mode, l0_ref_idx)) {
-    int j;
-    fr.ok_luma |= fr_luma_bits(block_x, block_y, block_size_x, block_size_y);
-    for (j = block_y; j < block_y + block_size_y; j++)
-      memcpy(&img->mpr[0][j][block_x], fr.pred[0] + (size_t)(img->pix_y + j) * g_w + img->pix_x + block_x, sizeof(imgpel) * (size_t)block_size_x);
-    width_pad = listX[LIST_0][l0_ref_idx]->size_x_pad; height_pad = listX[LIST_0][l0_ref_idx]->size_y_pad;      /* OneComponentLumaPrediction, macroblock.c:817-818 */
-    n_dev[S_LPRED]++;
-    return;
-  }
-  if (fr_rec_cur() && sl.active && fr_asks_candidate(block_x >> 2, block_y >> 2, (block_x + block_size_x) >> 2, (block_y + block_size_y) >> 2, p_dir, l0_mode, l0_ref_idx)) {
-    int j;
-    fr.ok_luma2 |= fr_luma_bits(block_x, block_y, block_size_x, block_size_y);
-    for (j = block_y; j < block_y + block_size_y; j++)
-      memcpy(&img->mpr[0][j][block_x], fr.pred2 + (size_t)(img->pix_y + j) * g_w + img->pix_x + block_x, sizeof(imgpel) * (size_t)block_size_x);
-    width_pad = listX[LIST_0][l0_ref_idx]->size_x_pad; height_pad = listX[LIST_0][l0_ref_idx]->size_y_pad;
-    n_dev[S_LPRED]++;
-    return;
+  const unsigned bits = fr_luma_bits(block_x, block_y, block_size_x, block_size_y);
+  if (fr_rec_cur()) { fr_ok_mb(); fr.ok_luma &= ~bits; fr.ok_luma2 &= ~bits; fr.ok_luma3 &= ~bits; }
+  if (fr_rec_cur() && sl.active && !fr_cost_scope) {
+    const int bx0 = block_x >> 2, by0 = block_y >> 2, bx1 = (block_x + block_size_x) >> 2, by1 = (block_y + block_size_y) >> 2;
+    /* the decision, the 4x4-transform candidate, the 8x8-transform candidate: the first pass that JM asks for answers the call; every pass that JM
+       asks for and whose prediction picture holds the same samples may answer the transform call that follows */
+    const int d = fr_asks_decided(bx0, by0, bx1, by1, p_dir, l0_mode, l0_ref_idx), c = fr_asks_candidate(bx0, by0, bx1, by1, p_dir, l0_mode, l0_ref_idx);
+    const int c8 = fr_asks_candidate8(bx0, by0, bx1, by1, p_dir, l0_mode, l0_ref_idx);
+    if (d || c || c8) {
+      const imgpel *src = d ? fr.pred[0] : c ? fr.pred2 : fr.pred3;
+      int j;
+      for (j = block_y; j < block_y + block_size_y; j++)
+        memcpy(&img->mpr[0][j][block_x], src + (size_t)(img->pix_y + j) * g_w + img->pix_x + block_x, sizeof(imgpel) * (size_t)block_size_x);
+      if (d) fr.ok_luma |= bits;
+      if (c && (!d || fr_same_pred(fr.pred2, block_x, block_y, block_size_x, block_size_y))) fr.ok_luma2 |= bits;
+      if (c8 && ((!d && !c) || fr_same_pred(fr.pred3, block_x, block_y, block_size_x, block_size_y))) fr.ok_luma3 |= bits;
+      width_pad = listX[LIST_0][l0_ref_idx]->size_x_pad; height_pad = listX[LIST_0][l0_ref_idx]->size_y_pad;      /* OneComponentLumaPrediction, macroblock.c:817-818 */
+      n_dev[S_LPRED]++;
+      return;
+    }
   }
   if (!orig) orig = next_sym("LumaPrediction");
-  if (fr_rec_cur()) n_fwd[S_LPRED]++;
+  if (fr_rec_cur()) n_fwd[fr_cost_scope ? S_LPREDC : S_LPRED]++;
   host_planes_lists();
   orig(currMB, block_x, block_y, block_size_x, block_size_y, p_dir, l0_mode, l1_mode, l0_ref_idx, l1_ref_idx);
 }
@@ -1249,7 +1322,7 @@ static int fr_dct4(Macroblock *currMB, int block_x, int block_y, int *coeff_cost
   fr_ok_mb();
   {
     const unsigned bit = 1u << ((block_y >> 2) * 4 + (block_x >> 2));
-    if (fr.ok_luma & bit) ;                                                      /* the decided block */
+    if ((fr.ok_luma & bit) && !(fr.t8 && fr.rec8[img->current_mb_nr - fr.mb_first].transform8x8)) ;      /* the decided block (of a 4x4-transform macroblock) */
     else if (fr.ok_luma2 & bit) { r = &fr.rec2[img->current_mb_nr - fr.mb_first]; pred0 = fr.pred2; }      /* the P8x8 candidate's block */
     else { n_fwd[S_D4R]++; return 0; }                                           /* JM's own prediction, so JM's transform */
   }
@@ -1273,6 +1346,54 @@ static int fr_dct4(Macroblock *currMB, int block_x, int block_y, int *coeff_cost
     }
     n_dev[S_D4R]++;
     *ret = (r->nonzero >> blk) & 1;
+    return 1;
+  }
+}
+
+/* dct_8x8 (src/transform8x8.c:1452) of an inter luma 8x8 block, from the decision's side records (an 8x8-transform macroblock) or those of the
+   8x8-transform P8x8 candidate -- whichever pass's prediction JM's img->mpr holds for the whole block */
+static int fr_dct8(Macroblock *currMB, int b8, int *coeff_cost, int *ret)
+{
+  const jmhip_mb_residual *r = fr_rec_cur();
+  const jmhip_mb_residual8 *r8;
+  const imgpel *pred0 = fr.pred[0];
+  const int block_x = 8 * (b8 & 1), block_y = 8 * (b8 >> 1);
+  const unsigned bits = fr_luma_bits(block_x, block_y, 8, 8);
+  int i8;
+  if (!r || !fr.t8 || IS_INTRA(currMB)) return 0;
+  fr_ok_mb();
+  i8 = img->current_mb_nr - fr.mb_first;
+  if ((fr.ok_luma & bits) == bits && fr.rec8[i8].transform8x8) r8 = &fr.rec8[i8];                                          /* the decided block */
+  else if (fr.have3 && (fr.ok_luma3 & bits) == bits) { r = &fr.rec3[i8]; r8 = &fr.rec83[i8]; pred0 = fr.pred3; }          /* the 8x8-transform candidate's */
+  else { n_fwd[S_D8R]++; return 0; }                                                                                       /* JM's own prediction, so JM's transform */
+  {
+    int **fa = img->AdaptiveRounding ? img->fadjust8x8[0] : NULL;
+    imgpel **img_enc = enc_picture->p_curr_img;
+    int j, i, k, n;
+    for (j = block_y; j < block_y + 8; j++) for (i = block_x; i < block_x + 8; i++) {
+      const int pr = pred0[(size_t)(img->pix_y + j) * g_w + img->pix_x + i];
+      if (img->mpr[0][j][i] != pr || img->m7[0][j][i] != pCurImg[img->opix_y + j][img->opix_x + i] - pr) fr_diverged("luma 8x8", block_x, block_y);
+    }
+    if (r8->interleaved)                      /* CAVLC: four interleaved lists cofAC[b8][0..3] (transform8x8.c:1502) */
+      for (k = 0; k < 4; k++) {
+        int *lev = img->cofAC[b8][k][0], *run = img->cofAC[b8][k][1];
+        n = r8->cnt[b8][k];
+        for (i = 0; i < n; i++) { lev[i] = r8->lev[b8][16 * k + i]; run[i] = r8->run[b8][16 * k + i]; }
+        lev[n] = 0;
+      }
+    else {
+      int *lev = img->cofAC[b8][0][0], *run = img->cofAC[b8][0][1];
+      n = r8->cnt[b8][0];
+      for (i = 0; i < n; i++) { lev[i] = r8->lev[b8][i]; run[i] = r8->run[b8][i]; }
+      lev[n] = 0;
+    }
+    *coeff_cost += r8->coeff_cost[b8];
+    for (j = block_y; j < block_y + 8; j++) for (i = block_x; i < block_x + 8; i++) {
+      img_enc[img->pix_y + j][img->pix_x + i] = r->recon_y[j][i];
+      if (fa) fa[j][i] = r->fadj_y[j][i];
+    }
+    n_dev[S_D8R]++;
+    *ret = r8->nonzero[b8];
     return 1;
   }
 }
