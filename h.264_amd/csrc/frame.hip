@@ -215,7 +215,7 @@ int jm_frame_buffers_ensure(jmhip_ctx *c, int n)
             hipMalloc(&c->fr_res_c, sizeof(jmhip_tq_result) * (size_t)n * 2) == hipSuccess &&
             hipMalloc(&c->fr_modes, (sizeof(jmhip_mb_mode) * 2 + sizeof(JmMbCoded)) * (size_t)n) == hipSuccess &&
             hipMalloc(&c->fr_blk_ref, 4 * (size_t)n) == hipSuccess &&
-            hipMalloc(&c->fr_rec, sizeof(JmMbRes) * (size_t)n) == hipSuccess;
+            hipMalloc(&c->fr_rec, (c->cfg.yuv_format == JMHIP_YUV422 ? sizeof(jmhip_mb_residual422) : sizeof(JmMbRes)) * (size_t)n) == hipSuccess;
   if (!ok) {                                            // leave nothing half-allocated behind (fr_capacity stays 0)
     for (auto b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage arrays");
@@ -352,10 +352,11 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
   F.wp_on = c->fr_wp.enable ? 1 : 0; F.wp_lround = c->fr_wp.luma_round; F.wp_ldenom = c->fr_wp.luma_denom; F.wp_cround = c->fr_wp.chroma_round; F.wp_cdenom = c->fr_wp.chroma_denom;
   for (int k = 0; k < 16; k++) for (int q = 0; q < 3; q++) { F.wp_w[k][q] = c->fr_wp.weight[k][q]; F.wp_o[k][q] = c->fr_wp.offset[k][q]; }
 
-  // 4:2:0 is ONE kernel that keeps the tiles on the CU and leaves a dense record per macroblock (tq.hip frame_fused_kernel); a picture with
-  // 8x8-transform macroblocks takes its T8 instantiation, which adds a jmhip_mb_residual8 side record per macroblock. JMHIP_FRAME_FUSED=0
-  // keeps the separate kernels (also taken by 4:2:2 and 4:0:0)
-  bool fused = F.yuv == JMHIP_YUV420 && quants[0].adapt_rnd_weight >= 0 && quants[0].adapt_rnd_weight < 32768 &&
+  // 4:2:0 and 4:2:2 are ONE kernel that keeps the tiles on the CU and leaves a dense record per macroblock (tq.hip frame_fused_kernel:
+  // jmhip_mb_residual, or jmhip_mb_residual422 from the 4:2:2 instantiations); a picture with 8x8-transform macroblocks takes a T8 instantiation,
+  // which adds a jmhip_mb_residual8 side record per macroblock. JMHIP_FRAME_FUSED=0 keeps the separate kernels (also taken by 4:0:0)
+  const bool f422 = F.yuv == JMHIP_YUV422;
+  bool fused = (F.yuv == JMHIP_YUV420 || (f422 && quants[2].adapt_rnd_weight >= 0 && quants[2].adapt_rnd_weight < 32768)) && quants[0].adapt_rnd_weight >= 0 && quants[0].adapt_rnd_weight < 32768 &&
                quants[1].adapt_rnd_weight >= 0 && quants[1].adapt_rnd_weight < 32768 &&
                (!any_t8 || (quants[3].adapt_rnd_weight >= 0 && quants[3].adapt_rnd_weight < 32768));
   if (const char *e = getenv("JMHIP_FRAME_FUSED")) if (!strcmp(e, "0")) fused = false;
@@ -370,10 +371,10 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
     rc = jm_launch_frame_fused(c, &F, c->me_jobs_dev, c->me_res_dev, modes_in_dev, modes_out_dev, c->fr_quant, c->fr_rec, coded_dev, n, any_t8 ? c->fr_rec8 : nullptr);
     jm_stage_end(c, JMHIP_STAGE_MC);                  // (the TQ stage has no launch of its own here: its time reads 0)
     if (rc) return rc;
-    c->fr_n = n; c->rec_valid = true; c->fr_fused = true; c->fr_fused8 = any_t8; c->pred_valid = c->keep_pred;
+    c->fr_n = n; c->rec_valid = true; c->fr_fused = true; c->fr_fused422 = f422; c->fr_fused8 = any_t8; c->pred_valid = c->keep_pred;
     return JMHIP_OK;
   }
-  c->fr_fused = false; c->fr_fused8 = false; c->pred_valid = false;
+  c->fr_fused = false; c->fr_fused422 = false; c->fr_fused8 = false; c->pred_valid = false;
   jm_stage_begin(c, JMHIP_STAGE_MC);
   mc_kernel<<<jm_xcd_grid(n), 64, 0, c->stream>>>(F, (const jmhip_me_mb *)c->me_jobs_dev, (const jmhip_me_result *)c->me_res_dev, modes_in_dev, modes_out_dev,
                                                   (jmhip_tq_job *)c->fr_jobs_y, (jmhip_tq_job *)c->fr_jobs_c, n);
@@ -400,10 +401,16 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
   if (!c) return JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_download: more macroblocks requested than processed");
   std::vector<JmMbRes> recs;
+  std::vector<jmhip_mb_residual422> recs422;
   std::vector<jmhip_mb_residual8> recs8;
   if (c->fr_fused && (luma || (chroma && c->Wc))) {
-    recs.resize(n);
-    JM_HIP_CHECK(c, hipMemcpyAsync(recs.data(), c->fr_rec, sizeof(JmMbRes) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (c->fr_fused422) {
+      recs422.resize(n);
+      JM_HIP_CHECK(c, hipMemcpyAsync(recs422.data(), c->fr_rec, sizeof(jmhip_mb_residual422) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    } else {
+      recs.resize(n);
+      JM_HIP_CHECK(c, hipMemcpyAsync(recs.data(), c->fr_rec, sizeof(JmMbRes) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
     if (c->fr_fused8 && luma) {
       recs8.resize(n);
       JM_HIP_CHECK(c, hipMemcpyAsync(recs8.data(), c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -423,9 +430,8 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n && (cbp || cbp_blk); i++) { if (cbp) cbp[i] = coded[i].cbp; if (cbp_blk) cbp_blk[i] = coded[i].cbp_blk; }
   // fused frame stage: expand the dense records into the ABI's result structs -- the fields the separate kernels write, zero elsewhere
-  for (int i = 0; i < n && !recs.empty(); i++) {
-    const JmMbRes &R = recs[i];
-    if (luma) {
+  auto expand_luma = [&](const auto &R, int i) {
+    {
       jmhip_tq_result &o = luma[i];
       memset(&o, 0, sizeof(o));
       for (int b = 0; b < 16; b++) {
@@ -446,6 +452,10 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
         }
       }
     }
+  };
+  for (int i = 0; i < n && !recs.empty(); i++) {
+    const JmMbRes &R = recs[i];
+    if (luma) expand_luma(R, i);
     for (int uv = 0; uv < 2 && chroma && c->Wc; uv++) {
       jmhip_tq_result &o = chroma[2 * i + uv];
       memset(&o, 0, sizeof(o));
@@ -456,6 +466,20 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
       o.ret = R.ret[uv]; o.cbp_blk = R.cbp_blk[uv]; o.cbp_clear = R.cbp_clear[uv];
     }
   }
+  // ... and the 4:2:2 records: eight AC lists, the 8-entry DC list and a 16 x 8 tile per component (what tq_chroma_kernel writes)
+  for (int i = 0; i < n && !recs422.empty(); i++) {
+    const jmhip_mb_residual422 &R = recs422[i];
+    if (luma) expand_luma(R, i);
+    for (int uv = 0; uv < 2 && chroma && c->Wc; uv++) {
+      jmhip_tq_result &o = chroma[2 * i + uv];
+      memset(&o, 0, sizeof(o));
+      for (int b = 0; b < 8; b++)
+        for (int k = 0; k < R.cnt[16 + 8 * uv + b]; k++) { o.levels[b][k] = R.ac_zeroed[uv] ? 0 : R.lev[16 + 8 * uv + b][k]; o.runs[b][k] = R.run[16 + 8 * uv + b][k]; }
+      for (int k = 0; k < R.dc_cnt[uv]; k++) { o.dc_levels[k] = R.dc_lev[uv][k]; o.dc_runs[k] = R.dc_run[uv][k]; }
+      for (int y = 0; y < 16; y++) for (int x = 0; x < 8; x++) { o.recon[y][x] = R.recon_c[uv][y][x]; if (c->fr_quant_host[1].adaptive_rounding) o.fadjust[y][x] = R.fadj_c[uv][y][x]; }
+      o.ret = R.ret[uv]; o.cbp_blk = R.cbp_blk[uv]; o.cbp_clear = R.cbp_clear[uv];
+    }
+  }
   return JMHIP_OK;
 }
 
@@ -463,9 +487,22 @@ extern "C" int jmhip_residual_records_download(jmhip_ctx *c, jmhip_mb_residual *
 {
   if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records_download: NULL") : JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records_download: more macroblocks requested than processed");
+  if (c->fr_fused && c->fr_fused422) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage took the fused 4:2:2 kernel (use jmhip_residual_records422_download)");
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage did not take the fused 4:2:0 kernel (use jmhip_residual_download)");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec, sizeof(jmhip_mb_residual) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return JMHIP_OK;
+}
+
+extern "C" int jmhip_residual_records422_download(jmhip_ctx *c, jmhip_mb_residual422 *records, int n)
+{
+  if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records422_download: NULL") : JMHIP_ERR_ARG;
+  if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records422_download: more macroblocks requested than processed");
+  if (c->fr_fused && !c->fr_fused422) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage took the fused 4:2:0 kernel (use jmhip_residual_records_download)");
+  if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage did not take the fused 4:2:2 kernel (use jmhip_residual_download)");
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec, sizeof(jmhip_mb_residual422) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -474,7 +511,7 @@ extern "C" int jmhip_residual_records8_download(jmhip_ctx *c, jmhip_mb_residual8
 {
   if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records8_download: NULL") : JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records8_download: more macroblocks requested than processed");
-  if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records8_download: the last frame stage did not take the fused 4:2:0 kernel (use jmhip_residual_download)");
+  if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records8_download: the last frame stage did not take the fused 4:2:0 / 4:2:2 kernel (use jmhip_residual_download)");
   if (!c->fr_fused8) { memset(records, 0, sizeof(jmhip_mb_residual8) * (size_t)n); return JMHIP_OK; }     // no 8x8-transform macroblock
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -505,7 +542,7 @@ extern "C" int jmhip_frame_keep_prediction(jmhip_ctx *c, int on)
 extern "C" int jmhip_pred_download(jmhip_ctx *c, void *Y, void *U, void *V, int pel_bytes)
 {
   if (!c) return JMHIP_ERR_ARG;
-  if (!c->pred_y || !c->pred_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_pred_download: no prediction picture (jmhip_frame_keep_prediction before a fused 4:2:0 jmhip_residual_frame)");
+  if (!c->pred_y || !c->pred_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_pred_download: no prediction picture (jmhip_frame_keep_prediction before a fused 4:2:0 / 4:2:2 jmhip_residual_frame)");
   int rc = Y ? jm_download_planes(c, c->pred_y, (size_t)c->W * c->H, Y, pel_bytes) : JMHIP_OK;
   if (rc) return rc;
   if (c->Wc && U && V) {

@@ -40,6 +40,7 @@ extern "C" int jmhip_sizeof(int which)
   case 21: return (int)sizeof(jmhip_frame_bw);
   case 22: return (int)sizeof(jmhip_mb_residual);
   case 23: return (int)sizeof(jmhip_mb_residual8);
+  case 24: return (int)sizeof(jmhip_mb_residual422);
   default: return -1;
   }
 }

@@ -55,8 +55,9 @@ struct jmhip_ctx {
   // frame pipeline (MC -> residual -> TQ -> recon): per-MB luma job/result, 2 chroma jobs/results, recon picture
   void *fr_jobs_y = nullptr, *fr_jobs_c = nullptr, *fr_res_y = nullptr, *fr_res_c = nullptr, *fr_quant = nullptr, *fr_modes = nullptr;
   int fr_capacity = 0, fr_n = 0;
-  void *fr_rec = nullptr;                             // fused frame stage: one JmMbRes record per macroblock (frame_common.h)
+  void *fr_rec = nullptr;                             // fused frame stage: one JmMbRes (4:2:2: jmhip_mb_residual422) record per macroblock (frame_common.h)
   bool fr_fused = false;                              // the last jmhip_residual_frame took the fused kernel: results live in fr_rec
+  bool fr_fused422 = false;                           // ... its 4:2:2 form: the records are jmhip_mb_residual422
   void *fr_rec8 = nullptr;                            // ... and one jmhip_mb_residual8 per macroblock when the picture has 8x8-transform macroblocks
   int fr_rec8_capacity = 0;
   bool fr_fused8 = false;                             // the last fused stage was the 8x8-transform instantiation: fr_rec8 holds its side records

@@ -19,6 +19,7 @@
 #include "jmhip_internal.h"
 #include "frame_common.h"
 #include <cstddef>
+#include <type_traits>
 
 namespace {
 
@@ -658,7 +659,7 @@ __global__ __launch_bounds__(256) void tq_chroma420_kernel(const jmhip_tq_job *_
 }
 
 
-// ---------------------------------------------------------------------------------------- fused 4:2:0 frame stage
+// ---------------------------------------------------------------------------------------- fused 4:2:0 / 4:2:2 frame stage
 //
 // mc_kernel + tq_luma4x4_kernel + tq_chroma420_kernel + finalize_kernel of the frame stage in ONE launch for the common case (4:2:0, 4x4
 // transform): the prediction and source tiles never leave the CU (registers for luma, 256 B of LDS for chroma) instead of travelling through
@@ -666,7 +667,7 @@ __global__ __launch_bounds__(256) void tq_chroma420_kernel(const jmhip_tq_job *_
 // sparse 5.8 KB structs. Four macroblocks per wave: in the luma phase every lane owns one 4x4 block (16 lanes per macroblock, JM order
 // b8*4+b4, so a DPP quad is an 8x8 block), in the chroma phase lanes 0..31 own the four Cb / four Cr blocks of each macroblock (a quad per
 // component, as tq_chroma420_kernel); all 64 lanes fetch the chroma prediction.
-// Same arithmetic, line for line, as the kernels it replaces (they stay for 4:2:2, 4:0:0, 8x8-transform macroblocks and jmhip_tq_batch).
+// Same arithmetic, line for line, as the kernels it replaces (they stay for 4:0:0, JMHIP_FRAME_FUSED=0 and jmhip_tq_batch).
 //
 // T8: the instantiation for pictures with 8x8-transform macroblocks (luma_transform_size_8x8_flag, mode pad[0]); 4x4-only pictures never select it.
 // In an 8x8-transform macroblock a quad is one 8x8 block: LumaPrediction per 8x8 block (UMV clamp at its origin, macroblock.c:1143), then dct_8x8
@@ -677,23 +678,33 @@ __device__ __forceinline__ void wave_lds_sync()       // LDS traffic between lan
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-static_assert(sizeof(jmhip_mb_residual8) % 16 == 0, "side records are copied out of LDS as 16-byte pieces");
+static_assert(sizeof(jmhip_mb_residual8) % 16 == 0 && sizeof(jmhip_mb_residual422) % 16 == 0, "records are copied out of LDS as 16-byte pieces");
 
-template <bool T8>
+// C422: the instantiations for 4:2:2 pictures. The luma phase is the same code; a macroblock's chroma is 2 components x 8 blocks of 4x4 (8 wide,
+// 16 high), so wave 1 is exactly one lane per block: 16 lanes per macroblock, 8 per component, block b = b8 * 4 + b4 of the component at column
+// 4 * (b & 1), row 4 * (b >> 1). dct_chroma's 4:2:2 branch as tq_chroma_kernel runs it (block.c:1051-1495), with JM's quirks: the swapped
+// forward4x4 arguments (block.c:1116-1122) transform chroma rows 0..7 only -- the four blocks of rows 8..15 are quantised as raw residual --; the
+// 2x4 DC transform over the eight lanes of a component (every lane gathers the eight DC terms and computes the cheap 8-entry list, the first lane
+// writes it, each lane keeps its own dequantised DC); the DC quantiser mixes the AC level scale with the offset, qp_per and inverse scale of
+// quants[2]; cbp_blk's int arithmetic sign-extends for Cr (block.c:1268). The record is jmhip_mb_residual422.
+template <bool T8, bool C422>
 __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhip_me_mb *__restrict__ mbs, const jmhip_me_result *__restrict__ me,
                                                         const jmhip_mb_mode *__restrict__ modes_in, jmhip_mb_mode *__restrict__ modes_out,
-                                                        const jmhip_quant *__restrict__ quants, JmMbRes *__restrict__ out, JmMbCoded *__restrict__ coded, int n,
+                                                        const jmhip_quant *__restrict__ quants,
+                                                        std::conditional_t<C422, jmhip_mb_residual422, JmMbRes> *__restrict__ out, JmMbCoded *__restrict__ coded, int n,
                                                         jmhip_mb_residual8 *__restrict__ out8)
 {
-  constexpr int NMB = 4;                               // macroblocks per wave: 16 luma lanes each, then 8 chroma lanes each
-  __shared__ __attribute__((aligned(16))) JmMbRes s_rec[NMB];
+  using Rec = std::conditional_t<C422, jmhip_mb_residual422, JmMbRes>;
+  constexpr int NMB = 4;                               // macroblocks per wave: 16 luma lanes each, then 8 (4:2:2: 16) chroma lanes each
+  constexpr int CH = C422 ? 16 : 8;                    // rows of a chroma component of one macroblock
+  __shared__ __attribute__((aligned(16))) Rec s_rec[NMB];
   __shared__ jmhip_mb_mode s_mode[NMB];
   __shared__ short s_mv[NMB][16][2];
   __shared__ int s_ref[NMB][4];
   __shared__ uint32_t s_mvall[NMB][JMHIP_NPART];
   __shared__ int s_cost[NMB][JMHIP_NPART];
   __shared__ short s_pos[NMB][2];
-  __shared__ __attribute__((aligned(4))) uint8_t s_pc[NMB][2][8][8], s_sc[NMB][2][8][8];      // chroma prediction / source tiles
+  __shared__ __attribute__((aligned(4))) uint8_t s_pc[NMB][2][CH][8], s_sc[NMB][2][CH][8];      // chroma prediction / source tiles
   __shared__ int s_t8[T8 ? 4 * NMB : 1][64];                                                 // T8: one coefficient tile per 8x8 block
   __shared__ __attribute__((aligned(16))) jmhip_mb_residual8 s_rec8[T8 ? NMB : 1];
   const int vb = jm_xcd_item((n + NMB - 1) / NMB);
@@ -751,7 +762,30 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
   }
   __syncthreads();
 
-  // ---- chroma prediction and source into LDS: four sample pairs per lane (mc_kernel's chroma loop, macroblock.c:1626-1650)
+  // ---- chroma prediction and source into LDS: four (4:2:2: eight) sample pairs per lane (mc_kernel's chroma loop, macroblock.c:1626-1650)
+  if constexpr (C422) {
+    // 4:2:2 geometry: eighth-pel columns, quarter-pel rows (shift_x 3, shift_y 2), 16 chroma rows per macroblock, a luma 4x4 block above every 4 rows
+    if (wv == 1)
+#pragma unroll
+    for (int t = tid; t < NMB * 128; t += 64) {
+      const int h = t >> 7, tt = t & 127;
+      const int mbx = s_pos[h][0], mby = s_pos[h][1];
+      const int uv = tt >> 6, q = tt & 63, j = q >> 2, ic = 2 * (q & 3);
+      const int by4 = j >> 2, bx4 = ic >> 1;
+      const short *mv = s_mv[h][by4 * 4 + bx4];
+      const int bii = ((ic + mbx * 8) << 3) + 4 * JMHIP_PAD, bjj = ((j + mby * 16) << 2) + 4 * JMHIP_PAD;
+      const int b8 = 2 * (by4 >> 1) + (bx4 >> 1), slot = s_ref[h][b8];
+      int pdir = 0, slot1 = 0;
+      if (F.bi) { const jmhip_mb_bipred &bm = F.bi[mb_of(h)]; pdir = bm.pdir[b8]; slot1 = bm.ref1[b8]; }
+      int p0 = 0, p1 = 0, q0 = 0, q1 = 0;
+      if (pdir != 1) chroma_pair(F, slot, uv, bii + mv[0], bjj + mv[1], &p0, &p1);
+      if (pdir != 0) { const short *m1 = F.bi[mb_of(h)].mv1[by4 * 4 + bx4]; chroma_pair(F, slot1, uv, bii + m1[0], bjj + m1[1], &q0, &q1); }
+      if (F.wp_on || pdir) { p0 = mix_pred(F, pdir, slot, slot1, uv + 1, p0, q0); p1 = mix_pred(F, pdir, slot, slot1, uv + 1, p1, q1); }
+      *reinterpret_cast<uint16_t *>(&s_pc[h][uv][j][ic]) = (uint16_t)(p0 | (p1 << 8));
+      const uint8_t *cs = (uv ? F.cur_v : F.cur_u) + (size_t)(mby * 16 + j) * F.Wc + mbx * 8 + ic;
+      *reinterpret_cast<uint16_t *>(&s_sc[h][uv][j][ic]) = *reinterpret_cast<const uint16_t *>(cs);
+    }
+  } else
   if (wv == 1)
 #pragma unroll
   for (int t = tid; t < NMB * 64; t += 64) {
@@ -779,7 +813,7 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
     const int h = tid >> 4, l = tid & 15;
     const int mbx = s_pos[h][0], mby = s_pos[h][1];
     const bool live = h < nlive;
-    JmMbRes &R = s_rec[h];
+    Rec &R = s_rec[h];
     const int blk = l, b8 = blk >> 2, b4 = blk & 3;
     const int x4 = 2 * (b8 & 1) + (b4 & 1), y4 = 2 * (b8 >> 1) + (b4 >> 1), bx = 4 * x4, by = 4 * y4;
     const jmhip_quant &q = quants[0];
@@ -1015,12 +1049,160 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
   }
   if (wv == 1) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }   // the chroma tiles are this wave's own
 
+  if constexpr (C422) {
+  if (wv == 1) {
+    // ---- chroma block: dct_chroma for 4:2:2, one lane per 4x4 block, eight lanes per component (tq_chroma_kernel), block.c:1051-1495
+    const int h = tid >> 4, uv = (tid >> 3) & 1, b = tid & 7, cb = 16 + 8 * uv + b;
+    const int mbx = s_pos[h][0], mby = s_pos[h][1];
+    const bool live = h < nlive;
+    Rec &R = s_rec[h];
+    const int bx = 4 * (b & 1), by = 4 * (b >> 1);
+    const jmhip_quant &q = quants[1], &qdc = quants[2];
+    const int qp_per = q.qp / 6, q_bits = Q_BITS + qp_per;
+    int m[4][4], pr[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t s = *reinterpret_cast<const uint32_t *>(&s_sc[h][uv][by + j][bx]);
+      const uint32_t p = *reinterpret_cast<const uint32_t *>(&s_pc[h][uv][by + j][bx]);
+#pragma unroll
+      for (int k = 0; k < 4; k++) { pr[j][k] = (p >> (8 * k)) & 255; m[j][k] = (int)((s >> (8 * k)) & 255) - pr[j][k]; }
+    }
+    // block.c:1116-1122 calls forward4x4(.., n1, n2) with row / column swapped: rows 0..7 (x columns 0..15, the upper half of which is empty) are
+    // transformed, the blocks of rows 8..15 stay raw residual. Mirrored, not fixed.
+    if (b < 4) fwd4(m);
+    // ---- 2x4 DC (block.c:1215-1316): m3[i][j] = the DC position of the block at column 4i, row 4j = lane 2j + i of the component's eight
+    int d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = __shfl(m[0][0], (tid & ~7) | k);
+    int m3[2][4], m4[2][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { m4[0][j] = d[2 * j] + d[2 * j + 1]; m4[1][j] = d[2 * j] - d[2 * j + 1]; }
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+      const int a0 = m4[i][0] + m4[i][3], a1 = m4[i][1] + m4[i][2], a2 = m4[i][1] - m4[i][2], a3 = m4[i][0] - m4[i][3];
+      m4[i][0] = a0 + a1; m4[i][2] = a0 - a1; m4[i][1] = a3 + a2; m4[i][3] = a3 - a2;
+    }
+    const int qp_per_dc = qdc.qp / 6, q_bits_422 = Q_BITS + qp_per_dc;
+    int run = -1, scan_pos = 0, DCcoded = 0, cr_cbp = 0;
+    long long cbp = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {          // every lane of the eight computes the (cheap) DC list; the first writes it
+      constexpr int SI[8] = {0, 0, 1, 0, 0, 1, 1, 1}, SJ[8] = {0, 1, 0, 2, 3, 1, 2, 3};     // SCAN_YUV422, block.h:52
+      const int i = SI[k], j = SJ[k];
+      run++;
+      const int level = (iabs(m4[i][j]) * q.levelscale[0] + (qdc.leveloffset[0] * 2)) >> (q_bits_422 + 1);   // block.c:1263: the AC level scale, the qp + 3 offset
+      if (level != 0) {
+        cbp |= (long long)(int)(0xff0000u << (uv << 3));     // block.c:1268 is int arithmetic: sign-extends for uv == 1 (JM quirk, kept)
+        cr_cbp = max(1, cr_cbp);
+        DCcoded = 1;
+        if (b == 0) { R.dc_lev[uv][scan_pos] = (int16_t)sgnab(level, m4[i][j]); R.dc_run[uv][scan_pos] = (uint8_t)run; }
+        scan_pos++;
+        run = -1;
+      }
+      m3[i][j] = sgnab(level, m4[i][j]);
+    }
+    if (b == 0) R.dc_cnt[uv] = (uint8_t)scan_pos;
+#pragma unroll
+    for (int j = 0; j < 4; j++) { m4[0][j] = m3[0][j] + m3[1][j]; m4[1][j] = m3[0][j] - m3[1][j]; }
+    {
+      int mine = 0;                                    // the inverse 2x4 output of this lane's block: column i = b & 1, row r = b >> 1
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int a0 = m4[i][0] + m4[i][2], a1 = m4[i][0] - m4[i][2], a2 = m4[i][1] - m4[i][3], a3 = m4[i][1] + m4[i][3];
+        const int v[4] = {a0 + a3, a1 + a2, a1 - a2, a0 - a3};
+#pragma unroll
+        for (int r = 0; r < 4; r++) mine = (b == 2 * r + i) ? v[r] : mine;
+      }
+      const int inv = qdc.invlevelscale[0];
+      m[0][0] = (qp_per_dc < 4) ? ((((mine * inv + (1 << (3 - qp_per_dc))) >> (4 - qp_per_dc)) + 2) >> 2)
+                                : ((((mine * inv) << (qp_per_dc - 4)) + 2) >> 2);                         // block.c:1303-1316
+    }
+    // ---- AC of this lane's block (scan positions 1..15)
+    int coeff_cost = 0, any = 0;
+    scan_pos = 0; run = -1;
+    int fa[4][4];
+    fa[0][0] = 0;                                      // the DC position is not dct_chroma's to write (block.c:1321: AC only)
+#pragma unroll
+    for (int k = 1; k < 16; k++) {
+      constexpr int I0[16] = {0,1,0,0,1,2,3,2,1,0,1,2,3,3,2,3}, J0[16] = {0,0,1,2,1,0,0,1,2,3,3,2,1,2,3,3};
+      constexpr int I1[16] = {0,0,1,0,0,1,1,1,2,2,2,2,3,3,3,3}, J1[16] = {0,1,0,2,3,1,2,3,0,1,2,3,0,1,2,3};
+      const int i0 = I0[k], j0 = J0[k], i1 = I1[k], j1 = J1[k];
+      const int c = q.field_scan ? m[j1][i1] : m[j0][i0];
+      const int idx = q.field_scan ? (j1 * 4 + i1) : (j0 * 4 + i0);
+      ++run;
+      const int scaled = iabs(c) * q.levelscale[idx];
+      int level = (scaled + q.leveloffset[idx]) >> q_bits;
+      int deq = 0, fadj = 0;
+      if (level != 0) {
+        if (q.adaptive_rounding) fadj = rsr(q.adapt_rnd_weight * (scaled - (level << q_bits)), q_bits + 1);
+        any = 1;
+        coeff_cost += (level > 1) ? MAXV : c_cost4[q.disthres][run];
+        level = sgnab(level, c);
+        R.lev[cb][scan_pos] = (int16_t)level; R.run[cb][scan_pos] = (uint8_t)run;
+        scan_pos++;
+        run = -1;
+        deq = rsr((level * q.invlevelscale[idx]) << qp_per, 4);
+      }
+      if (q.field_scan) { m[j1][i1] = deq; fa[j1][i1] = fadj; } else { m[j0][i0] = deq; fa[j0][i0] = fadj; }
+    }
+    R.cnt[cb] = (uint8_t)scan_pos;
+    if (q.adaptive_rounding) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) R.fadj_c[uv][by + j][bx + k] = (int16_t)fa[j][k];
+    }
+    if (any) cbp |= 1LL << (16 + 8 * uv + b);                             // cbp_blk_chroma[b8 + 2 * uv][b4], block.h:109
+    // ---- thresholding over the eight blocks of the component (_CHROMA_COEFF_COST_ = 4), block.c:1384-1410
+    int total = coeff_cost;
+    total += __builtin_amdgcn_update_dpp(total, total, 0xB1, 0xf, 0xf, false);
+    total += __builtin_amdgcn_update_dpp(total, total, 0x4E, 0xf, 0xf, false);
+    total += __shfl_xor(total, 4);
+    int any8 = any;
+    any8 |= __builtin_amdgcn_update_dpp(any8, any8, 0xB1, 0xf, 0xf, false);
+    any8 |= __builtin_amdgcn_update_dpp(any8, any8, 0x4E, 0xf, 0xf, false);
+    any8 |= __shfl_xor(any8, 4);
+    long long cbp_clear = 0;
+    int cr_cbp_tmp = any8 ? 2 : 0;
+    if (total < 4) {
+      cr_cbp_tmp = 0;
+      if (DCcoded == 0) cbp_clear = 0xff0000LL << (uv << 3);              // cbpblk_pattern[2] << (uv << 3)
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (k | j) m[j][k] = 0;
+    }
+    if (b == 0) R.ac_zeroed[uv] = (uint8_t)(total < 4);
+    if (cr_cbp_tmp == 2) cr_cbp = 2;
+    unsigned cl = (unsigned)cbp, ch = (unsigned)(cbp >> 32);             // the high half is the DC sign extension: the same on all eight lanes
+    cl |= (unsigned)__builtin_amdgcn_update_dpp((int)cl, (int)cl, 0xB1, 0xf, 0xf, false);
+    cl |= (unsigned)__builtin_amdgcn_update_dpp((int)cl, (int)cl, 0x4E, 0xf, 0xf, false);
+    cl |= (unsigned)__shfl_xor((int)cl, 4);
+    cbp = ((long long)ch << 32) | cl;
+    inv4(m);                                           // all eight blocks, rows 8..15 included: the inverse loop has its arguments in order (tq_chroma_kernel)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) w |= (uint32_t)clip1(q.max_val, rsr(m[j][k], DQ_BITS) + pr[j][k]) << (8 * k);
+      *reinterpret_cast<uint32_t *>(&R.recon_c[uv][by + j][bx]) = w;
+      if (live) *reinterpret_cast<uint32_t *>((uv ? F.rec_v : F.rec_u) + (size_t)(mby * 16 + by + j) * F.Wc + mbx * 8 + bx) = w;
+      if (live && F.pred_u) {
+        uint32_t pw = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) pw |= (uint32_t)pr[j][k] << (8 * k);
+        *reinterpret_cast<uint32_t *>((uv ? F.pred_v : F.pred_u) + (size_t)(mby * 16 + by + j) * F.Wc + mbx * 8 + bx) = pw;
+      }
+    }
+    if (b == 0) { R.ret[uv] = cr_cbp; R.cbp_blk[uv] = cbp & ~cbp_clear; R.cbp_clear[uv] = cbp_clear; }
+  }
+  } else
   if (wv == 1 && tid < 8 * NMB) {
     // ---- chroma block: dct_chroma for 4:2:0 on a quad of lanes (tq_chroma420_kernel), block.c:1051-1495
     const int h = tid >> 3, uv = (tid >> 2) & 1, b4 = tid & 3, cb = 16 + 4 * uv + b4;
     const int mbx = s_pos[h][0], mby = s_pos[h][1];
     const bool live = h < nlive;
-    JmMbRes &R = s_rec[h];
+    Rec &R = s_rec[h];
     const int bx = 4 * (b4 & 1), by = 4 * (b4 >> 1);
     const jmhip_quant &q = quants[1];
     const int qp_per = q.qp / 6, q_bits = Q_BITS + qp_per;
@@ -1135,7 +1317,7 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
   __syncthreads();
 
   if (wv == 0 && (tid & 15) == 0 && (tid >> 4) < nlive) {         // macroblock.c:2028-2040
-    const JmMbRes &R = s_rec[tid >> 4];
+    const Rec &R = s_rec[tid >> 4];
     const int i = i0 + (tid >> 4);
     long long cb = cbp_blk_luma;
     cb = (cb & ~R.cbp_clear[0]) | R.cbp_blk[0];
@@ -1145,7 +1327,7 @@ __global__ __launch_bounds__(128) void frame_fused_kernel(FrameDev F, const jmhi
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(s_rec);
     uint4 *dst = reinterpret_cast<uint4 *>(out + i0);
-    for (int k = threadIdx.x; k < nlive * (int)(sizeof(JmMbRes) / 16); k += 128) dst[k] = src[k];
+    for (int k = threadIdx.x; k < nlive * (int)(sizeof(Rec) / 16); k += 128) dst[k] = src[k];
   }
   if constexpr (T8) {
     const uint4 *src = reinterpret_cast<const uint4 *>(s_rec8);
@@ -1160,12 +1342,15 @@ int jm_launch_frame_fused(jmhip_ctx *c, const void *frame_dev, const void *mbs, 
                           const void *quants, void *records, void *coded, int n, void *records8)
 {
   const FrameDev &F = *static_cast<const FrameDev *>(frame_dev);
-  if (records8)
-    frame_fused_kernel<true><<<jm_xcd_grid((n + 3) / 4), 128, 0, c->stream>>>(F, (const jmhip_me_mb *)mbs, (const jmhip_me_result *)me, (const jmhip_mb_mode *)modes_in, (jmhip_mb_mode *)modes_out,
-                                                                           (const jmhip_quant *)quants, (JmMbRes *)records, (JmMbCoded *)coded, n, (jmhip_mb_residual8 *)records8);
-  else
-    frame_fused_kernel<false><<<jm_xcd_grid((n + 3) / 4), 128, 0, c->stream>>>(F, (const jmhip_me_mb *)mbs, (const jmhip_me_result *)me, (const jmhip_mb_mode *)modes_in, (jmhip_mb_mode *)modes_out,
-                                                                            (const jmhip_quant *)quants, (JmMbRes *)records, (JmMbCoded *)coded, n, nullptr);
+  const dim3 grid(jm_xcd_grid((n + 3) / 4));
+#define JM_FUSED(T8, C422, REC)                                                                                                                        \
+  frame_fused_kernel<T8, C422><<<grid, 128, 0, c->stream>>>(F, (const jmhip_me_mb *)mbs, (const jmhip_me_result *)me, (const jmhip_mb_mode *)modes_in, \
+                                                            (jmhip_mb_mode *)modes_out, (const jmhip_quant *)quants, (REC *)records, (JmMbCoded *)coded, n, \
+                                                            (jmhip_mb_residual8 *)records8)
+  if (F.yuv == JMHIP_YUV422) { if (records8) JM_FUSED(true, true, jmhip_mb_residual422); else JM_FUSED(false, true, jmhip_mb_residual422); }
+  else if (records8) JM_FUSED(true, false, JmMbRes);
+  else JM_FUSED(false, false, JmMbRes);
+#undef JM_FUSED
   if (hipGetLastError() != hipSuccess) return jm_fail(c, JMHIP_ERR_DEVICE, "frame_fused_kernel launch");
   return JMHIP_OK;
 }

@@ -136,6 +136,10 @@ MB_RESIDUAL_DTYPE = np.dtype([("lev", "<i2", (24, 16)), ("run", "u1", (24, 16)),
                               ("dc_cnt", "u1", (2,)), ("ac_zeroed", "u1", (2,)), ("pad0", "u1", (4,)), ("coeff_cost", "<i4", (16,)), ("ret", "<i4", (2,)),
                               ("nonzero", "<u2"), ("pad1", "<u2", (3,)), ("cbp_blk", "<i8", (2,)), ("cbp_clear", "<i8", (2,)), ("fadj_y", "<i2", (16, 16)),
                               ("fadj_c", "<i2", (2, 8, 8)), ("recon_y", "u1", (16, 16)), ("recon_c", "u1", (2, 8, 8)), ("pad2", "u1", (8,))])      # jmhip_mb_residual
+MB_RESIDUAL422_DTYPE = np.dtype([("lev", "<i2", (32, 16)), ("run", "u1", (32, 16)), ("cnt", "u1", (32,)), ("dc_lev", "<i2", (2, 8)), ("dc_run", "u1", (2, 8)),
+                                 ("dc_cnt", "u1", (2,)), ("ac_zeroed", "u1", (2,)), ("pad0", "u1", (4,)), ("coeff_cost", "<i4", (16,)), ("ret", "<i4", (2,)),
+                                 ("nonzero", "<u2"), ("pad1", "<u2", (3,)), ("cbp_blk", "<i8", (2,)), ("cbp_clear", "<i8", (2,)), ("fadj_y", "<i2", (16, 16)),
+                                 ("fadj_c", "<i2", (2, 16, 8)), ("recon_y", "u1", (16, 16)), ("recon_c", "u1", (2, 16, 8)), ("pad2", "u1", (8,))])      # jmhip_mb_residual422
 MB_RESIDUAL8_DTYPE = np.dtype([("lev", "<i2", (4, 64)), ("run", "u1", (4, 64)), ("cnt", "u1", (4, 4)), ("coeff_cost", "<i4", (4,)), ("nonzero", "<i4", (4,)),
                                ("transform8x8", "<i4"), ("interleaved", "<i4"), ("pad", "u1", (8,))])      # jmhip_mb_residual8
 TQ_RESULT_DTYPE = np.dtype([("levels", "<i4", (16, 17)), ("runs", "<i4", (16, 17)), ("levels8", "<i4", (4, 65)), ("runs8", "<i4", (4, 65)),
@@ -197,6 +201,7 @@ def load_library():
     lib.jmhip_recon_download.argtypes = [vp, vp, vp, vp, ip]
     lib.jmhip_residual_records_download.argtypes = [vp, vp, ip]
     lib.jmhip_residual_records8_download.argtypes = [vp, vp, ip]
+    lib.jmhip_residual_records422_download.argtypes = [vp, vp, ip]
     lib.jmhip_frame_keep_prediction.argtypes = [vp, ip]
     lib.jmhip_pred_download.argtypes = [vp, vp, vp, vp, ip]
     lib.jmhip_recon_copy_band.argtypes = [vp, vp, vp, vp, ip, ip]
@@ -237,7 +242,7 @@ def load_library():
     lib.jmhip_frame_bipred_set.argtypes = [vp, vp, ip, vp]
     for which, dt in ((0, ME_MB_DTYPE), (1, ME_RESULT_DTYPE), (2, QUANT_DTYPE), (3, TQ_JOB_DTYPE), (4, TQ_RESULT_DTYPE),
                       (5, DIST_JOB_DTYPE), (8, MB_MODE_DTYPE), (9, SURFACE_JOB_DTYPE), (10, BIPRED_JOB_DTYPE), (11, BIPRED_RESULT_DTYPE), (13, PREDCOST_JOB_DTYPE),
-                      (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE)):
+                      (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE), (24, MB_RESIDUAL422_DTYPE)):
         if lib.jmhip_sizeof(which) != dt.itemsize:
             raise JmhipError("binding layout mismatch for struct %d: C %d vs numpy %d" % (which, lib.jmhip_sizeof(which), dt.itemsize))
     if lib.jmhip_sizeof(6) != C.sizeof(MeParams) or lib.jmhip_sizeof(7) != C.sizeof(Config) or lib.jmhip_sizeof(12) != C.sizeof(BipredParams) or \
@@ -596,8 +601,14 @@ class Context:
         self._chk(self.lib.jmhip_residual_records_download(self.h, _ptr(rec), n), "jmhip_residual_records_download")
         return rec
 
+    def residual_records422(self, n):
+        """The dense per-macroblock records (jmhip_mb_residual422) of the last fused 4:2:2 residual_frame."""
+        rec = np.zeros(n, MB_RESIDUAL422_DTYPE)
+        self._chk(self.lib.jmhip_residual_records422_download(self.h, _ptr(rec), n), "jmhip_residual_records422_download")
+        return rec
+
     def residual_records8(self, n):
-        """The 8x8-transform side records (jmhip_mb_residual8) of the last fused 4:2:0 residual_frame: what dct_8x8 left behind per 8x8 block
+        """The 8x8-transform side records (jmhip_mb_residual8) of the last fused 4:2:0 / 4:2:2 residual_frame: what dct_8x8 left behind per 8x8 block
         of each macroblock with luma_transform_size_8x8_flag (all zero for the others)."""
         rec = np.zeros(n, MB_RESIDUAL8_DTYPE)
         self._chk(self.lib.jmhip_residual_records8_download(self.h, _ptr(rec), n), "jmhip_residual_records8_download")
@@ -607,7 +618,7 @@ class Context:
         self._chk(self.lib.jmhip_frame_keep_prediction(self.h, int(on)), "jmhip_frame_keep_prediction")
 
     def pred_download(self):
-        """The prediction picture (img->mpr of every macroblock) of the last fused 4:2:0 residual_frame."""
+        """The prediction picture (img->mpr of every macroblock) of the last fused 4:2:0 / 4:2:2 residual_frame."""
         Y = np.zeros((self.H, self.W), np.uint8)
         U = np.zeros((self.Hc, self.Wc), np.uint8) if self.Wc else None
         V = np.zeros((self.Hc, self.Wc), np.uint8) if self.Wc else None

@@ -563,7 +563,8 @@ int jmhip_residual_download(jmhip_ctx *ctx, jmhip_tq_result *luma, jmhip_tq_resu
 /* The dense per-macroblock record of the fused 4:2:0 frame stage: what JM's dct_4x4 x16 (src/block.c:843) and dct_chroma x2
  * (:1051) leave behind for one macroblock. jmhip_residual_records_download copies the records of the last jmhip_residual_frame as they are
  * (2.4 KB each; jmhip_residual_download expands them into three 5.8 KB jmhip_tq_result) -- the form a slice-level binding answers JM's
- * dct_4x4 / dct_chroma calls from. JMHIP_ERR_UNSUPPORTED when the last frame stage took the separate kernels (4:2:2, 4:0:0, JMHIP_FRAME_FUSED=0). */
+ * dct_4x4 / dct_chroma calls from. JMHIP_ERR_UNSUPPORTED when the last frame stage took the separate kernels (4:0:0, JMHIP_FRAME_FUSED=0) or was
+ * a 4:2:2 one, whose chroma this struct cannot hold (jmhip_residual_records422_download). */
 typedef struct jmhip_mb_residual {
   int16_t lev[24][16];           /* (level) lists in scan order: luma blocks 0..15 (JM order b8*4+b4), Cb 16..19, Cr 20..23 (AC) */
   uint8_t run[24][16];
@@ -585,9 +586,9 @@ typedef struct jmhip_mb_residual {
   uint8_t pad2[8];
 } jmhip_mb_residual;
 int jmhip_residual_records_download(jmhip_ctx *ctx, jmhip_mb_residual *records, int n);
-/* 8x8-transform macroblocks (luma_transform_size_8x8_flag, mode pad[0] = 1) of a 4:2:0 picture take the fused stage too. Their luma results
+/* 8x8-transform macroblocks (luma_transform_size_8x8_flag, mode pad[0] = 1) of a 4:2:0 or 4:2:2 picture take the fused stage too. Their luma results
  * are what dct_8x8 (src/transform8x8.c:1452-1653) leaves behind per 8x8 block, in this side record (832 bytes per macroblock). In the
- * jmhip_mb_residual of such a macroblock the luma lists, cnt[0..15], coeff_cost and nonzero read 0; recon_y and fadj_y hold the 8x8 path's
+ * jmhip_mb_residual (jmhip_mb_residual422) of such a macroblock the luma lists, cnt[0..15], coeff_cost and nonzero read 0; recon_y and fadj_y hold the 8x8 path's
  * reconstruction and fadjust8x8; the chroma fields keep their meaning. jmhip_residual_records8_download copies the side records of the last
  * jmhip_residual_frame (all zero when it had no 8x8-transform macroblock); JMHIP_ERR_UNSUPPORTED when it took the separate kernels. */
 typedef struct jmhip_mb_residual8 {
@@ -602,8 +603,37 @@ typedef struct jmhip_mb_residual8 {
   uint8_t pad[8];
 } jmhip_mb_residual8;
 int jmhip_residual_records8_download(jmhip_ctx *ctx, jmhip_mb_residual8 *records, int n);
+/* The dense per-macroblock record of the fused 4:2:2 frame stage (3280 bytes): the luma fields of jmhip_mb_residual with the same meaning
+ * (lists 0..15, cnt, coeff_cost, nonzero, fadj_y, recon_y; 0 for an 8x8-transform macroblock, whose lists are in jmhip_mb_residual8 as for 4:2:0)
+ * and what dct_chroma (src/block.c:1051-1495, the 4:2:2 branch) leaves behind for the two 8-wide, 16-high components: eight AC lists per
+ * component in JM's block order b8 * 4 + b4 (the 4x4 block at column 4 * (b & 1), row 4 * (b >> 1) of the component), the 8-entry list of the
+ * 2x4 DC transform (scan order of SCAN_YUV422, inc/block.h:52), and the per-component results with the meaning they have in jmhip_mb_residual.
+ * cbp_blk of Cr carries JM's sign extension (block.c:1268: 0xff0000 << 8 in int arithmetic) when a Cr DC level is coded.
+ * jmhip_residual_records422_download copies the records of the last jmhip_residual_frame when it took the fused 4:2:2 form;
+ * JMHIP_ERR_UNSUPPORTED otherwise (4:2:0: jmhip_residual_records_download; separate kernels: jmhip_residual_download). */
+typedef struct jmhip_mb_residual422 {
+  int16_t lev[32][16];           /* (level) lists in scan order: luma blocks 0..15 (JM order b8*4+b4), Cb 16..23, Cr 24..31 (AC, b8*4+b4 per component) */
+  uint8_t run[32][16];
+  uint8_t cnt[32];               /* entries of each list; JM's 0 terminator follows them */
+  int16_t dc_lev[2][8];          /* chroma DC lists (2x4 transform) */
+  uint8_t dc_run[2][8];
+  uint8_t dc_cnt[2];
+  uint8_t ac_zeroed[2];          /* _CHROMA_COEFF_COST_ thresholding hit: the AC levels of the component's eight blocks read 0, the runs stay (block.c:1384-1410) */
+  uint8_t pad0[4];
+  int32_t coeff_cost[16];        /* luma, per 4x4 block: what dct_4x4 adds to *coeff_cost */
+  int32_t ret[2];                /* dct_chroma's return value (cr_cbp) per component */
+  uint16_t nonzero;              /* luma: bit blk = dct_4x4's return value */
+  uint16_t pad1[3];
+  int64_t cbp_blk[2], cbp_clear[2];   /* dct_chroma: currMB->cbp_blk = (cbp_blk & ~cbp_clear) | cbp_blk */
+  int16_t fadj_y[16][16];        /* adaptive rounding only: img->fadjust4x4 (fadjust8x8) / fadjust4x4Cr */
+  int16_t fadj_c[2][16][8];
+  uint8_t recon_y[16][16];       /* the transform path's reconstruction (before the caller's coefficient-cost decision) */
+  uint8_t recon_c[2][16][8];
+  uint8_t pad2[8];
+} jmhip_mb_residual422;
+int jmhip_residual_records422_download(jmhip_ctx *ctx, jmhip_mb_residual422 *records, int n);
 /* Keep the prediction picture -- img->mpr of every macroblock of jmhip_residual_frame, luma and chroma (src/macroblock.c:836, :1593) -- beside
- * the recon picture (fused 4:2:0 stage only), and copy it to the host (pel_bytes 1 or 2): a binding that answers JM's LumaPrediction /
+ * the recon picture (fused 4:2:0 / 4:2:2 stage only), and copy it to the host (pel_bytes 1 or 2): a binding that answers JM's LumaPrediction /
  * ChromaPrediction4x4 from the device reads it, and checks its dct inputs against it. */
 int jmhip_frame_keep_prediction(jmhip_ctx *ctx, int on);
 int jmhip_pred_download(jmhip_ctx *ctx, void *Y, void *U, void *V, int pel_bytes);
@@ -668,7 +698,7 @@ int jmhip_ref_unpack_bands(jmhip_ctx *ctx, int ref, const void *chunks_device, i
  * 2 jmhip_quant, 3 jmhip_tq_job, 4 jmhip_tq_result, 5 jmhip_dist_job, 6 jmhip_me_params, 7 jmhip_config,
  * 8 jmhip_mb_mode, 9 jmhip_surface_job, 10 jmhip_bipred_job, 11 jmhip_bipred_result, 12 jmhip_bipred_params, 13 jmhip_predcost_job,
  * 14 jmhip_deblock_mb, 15 jmhip_deblock_blk, 16 jmhip_deblock_params, 17 jmhip_slice_params, 18 jmhip_mb_inter, 19 jmhip_frame_wp,
- * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8. */
+ * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8, 24 jmhip_mb_residual422. */
 int jmhip_sizeof(int which);
 
 /* Flat (no scaling matrix) tables: CalculateQuantParam / CalculateQuant8Param (src/q_matrix.c:451,590) and
