@@ -41,6 +41,9 @@ extern "C" int jmhip_sizeof(int which)
   case 22: return (int)sizeof(jmhip_mb_residual);
   case 23: return (int)sizeof(jmhip_mb_residual8);
   case 24: return (int)sizeof(jmhip_mb_residual422);
+  case 30: return (int)sizeof(jmhip_bipred_chain_job);
+  case 31: return (int)sizeof(jmhip_bipred_chain_params);
+  case 32: return (int)sizeof(jmhip_bipred_chain_result);
   default: return -1;
   }
 }
@@ -124,6 +127,7 @@ extern "C" void jmhip_ctx_destroy(jmhip_ctx *c)
   if (c->pin_host) (void)hipHostFree(c->pin_host);
   for (auto e : c->pin_evt) (void)hipEventDestroy(e);
   (void)hipFree(c->stage_dev); (void)hipFree(c->me_jobs_dev); (void)hipFree(c->me_res_dev); (void)hipFree(c->ref_ptrs_dev); (void)hipFree(c->me_idx_dev); (void)hipFree(c->surf_dev); (void)hipFree(c->surf_jobs_dev);
+  (void)hipFree(c->bic_jobs_dev); (void)hipFree(c->bic_res_dev);
   (void)hipFree(c->tq_jobs_dev); (void)hipFree(c->tq_res_dev); (void)hipFree(c->tq_quant_dev);
   (void)hipFree(c->fr_bi); (void)hipFree(c->fr_rec); (void)hipFree(c->fr_rec8); (void)hipFree(c->fr_blk_ref); (void)hipFree(c->fr_jobs_y); (void)hipFree(c->fr_jobs_c); (void)hipFree(c->fr_res_y); (void)hipFree(c->fr_res_c);
   jm_slice_state_free(c);

@@ -2,6 +2,7 @@
 //   distortion_kernel    computeSAD / SADWP / SATD / SATDWP for arbitrary candidate lists           (jmhip_distortion_batch)
 //   surface_kernel<K>    every integer displacement in early-exit granularity, for EPZS / UMHexagonS (jmhip_distortion_surface)
 //   bipred_kernel        FullPelBlockMotionBiPred / SubPelBlockSearchBiPred                          (jmhip_bipred_search)
+//   bipred_chain_kernel  the bi-predictive refinement chain of BlockMotionSearch, one launch per chain     (jmhip_bipred_chain)
 //   predcost_kernel      TransformDecision / GetSkipCostMB / BIDPartitionCost residual costs         (jmhip_pred_cost_batch)
 #include "me_common.h"
 
@@ -299,109 +300,125 @@ __device__ __forceinline__ uint32_t bipel4(const BiDev &B, uint32_t a, uint32_t 
   return r;
 }
 
-__global__ __launch_bounds__(256) void bipred_kernel(BiDev B, const jmhip_bipred_job *__restrict__ jobs, jmhip_bipred_result *__restrict__ res)
+// The LDS of one bi-predictive workgroup beside the dynamic window: the current block (bytes, and packed 16-bit with the SATD bias),
+// the fixed block of the integer stage and the reduction cells of both stages.
+struct BiLds {
+  uint8_t cur[16][16];
+  uint32_t c16[16][8];
+  uint32_t fix[16][4];              // integer stage: the fixed 16x16 block of picture 1
+  unsigned best;
+  int satd[9], swept[2], min_mcost; // sub-pel stage: candidate sums, the swept vector (in / out) and the carried minimum (in / out)
+};
+
+// one search call: pictures, vectors and predictors in JM's "1" = fixed / "2" = swept naming
+struct BiCall { int ref1, ref2, smvx, smvy, p1x, p1y, p2x, p2y; };
+
+__device__ __forceinline__ void bi_stage_cur(const BiDev &B, BiLds &L, int ox, int oy)
 {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ __attribute__((aligned(16))) uint8_t s_cur[16][16];
-  __shared__ __attribute__((aligned(16))) uint32_t s_c16[16][8];
-  __shared__ uint32_t s_fix[16][4];                 // stage 0: the fixed 16x16 block of picture 1
-  __shared__ unsigned s_best;
-  __shared__ int s_satd[9], s_mv[2], s_min;
-  const jmhip_bipred_job job = jobs[blockIdx.x];
   const int tid = threadIdx.x;
-  const int ox = job.mb_x * 16, oy = job.mb_y * 16;
   if (tid < 64) {
     const int r = tid >> 2, k = tid & 3;
     const uint32_t v = *reinterpret_cast<const uint32_t *>(B.cur + (size_t)(oy + r) * B.W + ox + k * 4);
-    *reinterpret_cast<uint32_t *>(&s_cur[r][k * 4]) = v;
+    *reinterpret_cast<uint32_t *>(&L.cur[r][k * 4]) = v;
     const uint32_t bias = (r & 3) ? 0u : 0x80000000u;
-    s_c16[r][2 * k] = __builtin_amdgcn_perm(0u, v, 0x0c010c00u) + bias;
-    s_c16[r][2 * k + 1] = __builtin_amdgcn_perm(0u, v, 0x0c030c02u);
+    L.c16[r][2 * k] = __builtin_amdgcn_perm(0u, v, 0x0c010c00u) + bias;
+    L.c16[r][2 * k + 1] = __builtin_amdgcn_perm(0u, v, 0x0c030c02u);
   }
-  if (tid == 0) s_best = 0xffffffffu;
+}
 
-  if (job.stage == 0) {
-    // ---------------- FullPelBlockMotionBiPred: integer planes, per-sample clamp == UMV origin clamp on the 20-pel ring
-    const int R = job.search_range, UW = 2 * R + 1;
-    const int pitch = (UW + 15 + 3 + 4) & ~3;
-    const uint8_t *ref1 = B.ref_y[job.ref1], *ref2 = B.ref_y[job.ref2];
-    const int bx = ox + job.mv[0] - R, by = oy + job.mv[1] - R;
-    for (int d = tid; d < (pitch >> 2) * (UW + 15); d += 256) {
-      const int y = d / (pitch >> 2), xw = d - y * (pitch >> 2);
-      const uint8_t *row = ref2 + (size_t)clampi(by + y, 0, B.H - 1) * B.W;
-      uint32_t v = 0;
+// FullPelBlockMotionBiPred (me_fullsearch.c:164): integer planes, per-sample clamp == UMV origin clamp on the 20-pel ring. Stages the window
+// of picture 2 round (mvx, mvy) and the fixed block of picture 1, evaluates the (2R+1)^2 candidates and returns to every thread the packed
+// minimum (cost << TIE_BITS | spiral position). L.cur must be staged (this function's first barrier publishes it); two barriers inside,
+// the caller puts one more before the next call.
+__device__ __forceinline__ unsigned bi_fullpel(const BiDev &B, BiLds &L, uint8_t *smem, int ox, int oy, const BiCall &q, int mvx0, int mvy0, int R)
+{
+  const int tid = threadIdx.x;
+  const int UW = 2 * R + 1;
+  const int pitch = (UW + 15 + 3 + 4) & ~3;
+  const uint8_t *ref1 = B.ref_y[q.ref1], *ref2 = B.ref_y[q.ref2];
+  const int bx = ox + mvx0 - R, by = oy + mvy0 - R;
+  if (tid == 0) L.best = 0xffffffffu;
+  for (int d = tid; d < (pitch >> 2) * (UW + 15); d += 256) {
+    const int y = d / (pitch >> 2), xw = d - y * (pitch >> 2);
+    const uint8_t *row = ref2 + (size_t)clampi(by + y, 0, B.H - 1) * B.W;
+    uint32_t v = 0;
 #pragma unroll
-      for (int k = 0; k < 4; k++) v |= (uint32_t)row[clampi(bx + xw * 4 + k, 0, B.W - 1)] << (8 * k);
-      *reinterpret_cast<uint32_t *>(smem + (size_t)y * pitch + xw * 4) = v;
-    }
-    if (tid < 64) {
-      const int r = tid >> 2, k = tid & 3;
-      const uint8_t *row = ref1 + (size_t)clampi(oy + job.s_mv[1] + r, 0, B.H - 1) * B.W;
-      uint32_t v = 0;
-#pragma unroll
-      for (int j = 0; j < 4; j++) v |= (uint32_t)row[clampi(ox + job.s_mv[0] + k * 4 + j, 0, B.W - 1)] << (8 * j);
-      s_fix[r][k] = v;
-    }
-    __syncthreads();
-    const int c1 = mv_cost(B.lam_f, 4 * job.s_mv[0] - job.pred1[0], 4 * job.s_mv[1] - job.pred1[1]);
-    unsigned best = 0xffffffffu;
-    for (int c = tid; c < UW * UW; c += 256) {
-      const int ay = c / UW, ax = c - ay * UW;
-      const uint8_t *wrow = smem + (size_t)ay * pitch + (ax & ~3);
-      const unsigned sh = ax & 3;
-      unsigned sad = 0;
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const uint32_t *wp = reinterpret_cast<const uint32_t *>(wrow + (size_t)r * pitch);
-        const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2], d3 = wp[3], d4 = wp[4];
-        const uint32_t *cw = reinterpret_cast<const uint32_t *>(&s_cur[r][0]);
-        sad = __builtin_amdgcn_sad_u8(bipel4(B, s_fix[r][0], __builtin_amdgcn_alignbyte(d1, d0, sh)), cw[0], sad);
-        sad = __builtin_amdgcn_sad_u8(bipel4(B, s_fix[r][1], __builtin_amdgcn_alignbyte(d2, d1, sh)), cw[1], sad);
-        sad = __builtin_amdgcn_sad_u8(bipel4(B, s_fix[r][2], __builtin_amdgcn_alignbyte(d3, d2, sh)), cw[2], sad);
-        sad = __builtin_amdgcn_sad_u8(bipel4(B, s_fix[r][3], __builtin_amdgcn_alignbyte(d4, d3, sh)), cw[3], sad);
-      }
-      const int mvx = job.mv[0] - R + ax, mvy = job.mv[1] - R + ay;
-      const unsigned cost = (unsigned)(c1 + mv_cost(B.lam_f, 4 * mvx - job.pred2[0], 4 * mvy - job.pred2[1])) + sad;
-      best = min(best, (cost << TIE_BITS) | (unsigned)spiral_pos(ax - R, ay - R));
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, off, 64));
-    if ((tid & 63) == 0) atomicMin(&s_best, best);
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned k = s_best;
-      const int cost = (int)(k >> TIE_BITS);
-      int dx = 0, dy = 0;
-      jmhip_bipred_result o;
-      if (cost < job.min_mcost) { spiral_offset((int)(k & ((1u << TIE_BITS) - 1)), &dx, &dy); o.cost = cost; }
-      else o.cost = job.min_mcost;
-      o.mv[0] = (int16_t)(job.mv[0] + dx); o.mv[1] = (int16_t)(job.mv[1] + dy);
-      res[blockIdx.x] = o;
-    }
-    return;
+    for (int k = 0; k < 4; k++) v |= (uint32_t)row[clampi(bx + xw * 4 + k, 0, B.W - 1)] << (8 * k);
+    *reinterpret_cast<uint32_t *>(smem + (size_t)y * pitch + xw * 4) = v;
   }
+  if (tid < 64) {
+    const int r = tid >> 2, k = tid & 3;
+    const uint8_t *row = ref1 + (size_t)clampi(oy + q.smvy + r, 0, B.H - 1) * B.W;
+    uint32_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) v |= (uint32_t)row[clampi(ox + q.smvx + k * 4 + j, 0, B.W - 1)] << (8 * j);
+    L.fix[r][k] = v;
+  }
+  __syncthreads();
+  const int c1 = mv_cost(B.lam_f, 4 * q.smvx - q.p1x, 4 * q.smvy - q.p1y);
+  unsigned best = 0xffffffffu;
+  for (int c = tid; c < UW * UW; c += 256) {
+    const int ay = c / UW, ax = c - ay * UW;
+    const uint8_t *wrow = smem + (size_t)ay * pitch + (ax & ~3);
+    const unsigned sh = ax & 3;
+    unsigned sad = 0;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const uint32_t *wp = reinterpret_cast<const uint32_t *>(wrow + (size_t)r * pitch);
+      const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2], d3 = wp[3], d4 = wp[4];
+      const uint32_t *cw = reinterpret_cast<const uint32_t *>(&L.cur[r][0]);
+      sad = __builtin_amdgcn_sad_u8(bipel4(B, L.fix[r][0], __builtin_amdgcn_alignbyte(d1, d0, sh)), cw[0], sad);
+      sad = __builtin_amdgcn_sad_u8(bipel4(B, L.fix[r][1], __builtin_amdgcn_alignbyte(d2, d1, sh)), cw[1], sad);
+      sad = __builtin_amdgcn_sad_u8(bipel4(B, L.fix[r][2], __builtin_amdgcn_alignbyte(d3, d2, sh)), cw[2], sad);
+      sad = __builtin_amdgcn_sad_u8(bipel4(B, L.fix[r][3], __builtin_amdgcn_alignbyte(d4, d3, sh)), cw[3], sad);
+    }
+    const int mvx = mvx0 - R + ax, mvy = mvy0 - R + ay;
+    const unsigned cost = (unsigned)(c1 + mv_cost(B.lam_f, 4 * mvx - q.p2x, 4 * mvy - q.p2y)) + sad;
+    best = min(best, (cost << TIE_BITS) | (unsigned)spiral_pos(ax - R, ay - R));
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, off, 64));
+  if ((tid & 63) == 0) atomicMin(&L.best, best);
+  __syncthreads();
+  return L.best;
+}
 
-  // ---------------- SubPelBlockSearchBiPred: quarter-pel planes, origin clamp per SATD sub-block of BOTH pictures
-  const uint8_t *sub1 = B.ref_sub[job.ref1], *sub2 = B.ref_sub[job.ref2];
+// what the call hands back: a candidate below the carried minimum moves the vector, otherwise the centre and the minimum return (:317-331)
+__device__ __forceinline__ int bi_fullpel_accept(unsigned key, int min_mcost, int *mvx, int *mvy)
+{
+  const int cost = (int)(key >> TIE_BITS);
+  if (cost >= min_mcost) return min_mcost;
+  int dx = 0, dy = 0;
+  spiral_offset((int)(key & ((1u << TIE_BITS) - 1)), &dx, &dy);
+  *mvx += dx; *mvy += dy;
+  return cost;
+}
+
+// SubPelBlockSearchBiPred (me_fullsearch.c:520): quarter-pel planes, origin clamp per SATD sub-block of BOTH pictures. Thread 0 has put the
+// swept vector into L.swept and the carried minimum into L.min_mcost (this function's first barrier publishes them, and L.cur / L.c16); the
+// refined vector and the minimum come back in the same cells, after a barrier.
+__device__ __forceinline__ void bi_subpel(const BiDev &B, BiLds &L, int ox, int oy, const BiCall &q)
+{
+  const int tid = threadIdx.x;
+  const uint8_t *sub1 = B.ref_sub[q.ref1], *sub2 = B.ref_sub[q.ref2];
   const size_t plane = (size_t)B.Wp * B.Hp;
   const int width_pad = B.Wp - 1 - 16, height_pad = B.Hp - 1 - 16;
   const int p4x = (ox + JMHIP_PAD) << 2, p4y = (oy + JMHIP_PAD) << 2;
   const int max_x4 = (B.W - 16 + 2 * JMHIP_PAD) << 2, max_y4 = (B.H - 16 + 2 * JMHIP_PAD) << 2;
   const int nblk = B.t8x8 ? 4 : 16, bs = B.t8x8 ? 8 : 4;
-  if (tid == 0) { s_mv[0] = job.mv[0]; s_mv[1] = job.mv[1]; s_min = job.min_mcost; }
   for (int phase = 0; phase < 2; phase++) {        // start_me_refinement_hp == 0, _qp == 1 (SAD full-pel, SATD sub-pel)
     const int step = phase ? 1 : 2, first = phase ? 1 : 0, ncand = 9 - first;
-    if (tid < 9) s_satd[tid] = 0;
+    if (tid < 9) L.satd[tid] = 0;
     __syncthreads();
-    const int mvx = s_mv[0], mvy = s_mv[1];
+    const int mvx = L.swept[0], mvy = L.swept[1];
     const int m = phase ? 0 : 1;                     // me_fullsearch.c:642-661 vs :694-713
     const int umv2 = !((p4x + mvx > m) && (p4x + mvx < max_x4 - m) && (p4y + mvy > m) && (p4y + mvy < max_y4 - m));
-    const int umv1 = !((p4x + job.s_mv[0] > m) && (p4x + job.s_mv[0] < max_x4 - m) && (p4y + job.s_mv[1] > m) && (p4y + job.s_mv[1] < max_y4 - m));
+    const int umv1 = !((p4x + q.smvx > m) && (p4x + q.smvx < max_x4 - m) && (p4y + q.smvy > m) && (p4y + q.smvy < max_y4 - m));
     for (int idx = tid; idx < nblk * ncand; idx += 256) {
       const int ci = idx / nblk, b = idx - ci * nblk, cand = first + ci;
       const int bxo = B.t8x8 ? 8 * (b & 1) : 4 * (b & 3), byo = B.t8x8 ? 8 * (b >> 1) : 4 * (b >> 2);
       const int x2 = p4x + mvx + step * c_s9x[cand] + (bxo << 2), y2 = p4y + mvy + step * c_s9y[cand] + (byo << 2);
-      const int x1 = p4x + job.s_mv[0] + (bxo << 2), y1 = p4y + job.s_mv[1] + (byo << 2);
+      const int x1 = p4x + q.smvx + (bxo << 2), y1 = p4y + q.smvy + (byo << 2);
       int xp2 = x2 >> 2, yp2 = y2 >> 2, xp1 = x1 >> 2, yp1 = y1 >> 2;
       if (umv2) { xp2 = clampi(xp2, 0, width_pad); yp2 = clampi(yp2, 0, height_pad); }
       if (umv1) { xp1 = clampi(xp1, 0, width_pad); yp1 = clampi(yp1, 0, height_pad); }
@@ -416,7 +433,7 @@ __global__ __launch_bounds__(256) void bipred_kernel(BiDev B, const jmhip_bipred
           fetch_row(r1 + (size_t)r * B.Wp, 4, &a, &hi);
           fetch_row(r2 + (size_t)r * B.Wp, 4, &bq, &hi);
           rf[r] = bipel4(B, a, bq);
-          c01[r] = s_c16[byo + r][bxo >> 1]; c23[r] = s_c16[byo + r][(bxo >> 1) + 1];
+          c01[r] = L.c16[byo + r][bxo >> 1]; c23[r] = L.c16[byo + r][(bxo >> 1) + 1];
         }
         v = satd4x4_packed(c01, c23, rf);
       } else {
@@ -427,7 +444,7 @@ __global__ __launch_bounds__(256) void bipred_kernel(BiDev B, const jmhip_bipred
           fetch_row(r1 + (size_t)r * B.Wp, 8, &a0, &a1);
           fetch_row(r2 + (size_t)r * B.Wp, 8, &b0, &b1);
           const uint32_t lo = bipel4(B, a0, b0), hi = bipel4(B, a1, b1);
-          const uint32_t c0 = *reinterpret_cast<const uint32_t *>(&s_cur[byo + r][bxo]), c1 = *reinterpret_cast<const uint32_t *>(&s_cur[byo + r][bxo + 4]);
+          const uint32_t c0 = *reinterpret_cast<const uint32_t *>(&L.cur[byo + r][bxo]), c1 = *reinterpret_cast<const uint32_t *>(&L.cur[byo + r][bxo + 4]);
           int row[8];
 #pragma unroll
           for (int x = 0; x < 4; x++) { row[x] = (int)((c0 >> (8 * x)) & 255) - (int)((lo >> (8 * x)) & 255); row[4 + x] = (int)((c1 >> (8 * x)) & 255) - (int)((hi >> (8 * x)) & 255); }
@@ -447,23 +464,139 @@ __global__ __launch_bounds__(256) void bipred_kernel(BiDev B, const jmhip_bipred
         }
         v = (s + 2) >> 2;
       }
-      atomicAdd(&s_satd[cand], v);
+      atomicAdd(&L.satd[cand], v);
     }
     __syncthreads();
     if (tid == 0) {
       const int lam = phase ? B.lam_q : B.lam_h;
-      int min_mcost = s_min, best = 0;
+      int min_mcost = L.min_mcost, best = 0;
       for (int pos = first; pos < 9; pos++) {
-        int mcost = mv_cost(lam, mvx + step * c_s9x[pos] - job.pred2[0], mvy + step * c_s9y[pos] - job.pred2[1]);
+        int mcost = mv_cost(lam, mvx + step * c_s9x[pos] - q.p2x, mvy + step * c_s9y[pos] - q.p2y);
         if (mcost >= min_mcost) continue;
-        mcost += s_satd[pos];
+        mcost += L.satd[pos];
         if (mcost < min_mcost) { min_mcost = mcost; best = pos; }
       }
-      s_mv[0] = mvx + step * c_s9x[best]; s_mv[1] = mvy + step * c_s9y[best]; s_min = min_mcost;
+      L.swept[0] = mvx + step * c_s9x[best]; L.swept[1] = mvy + step * c_s9y[best]; L.min_mcost = min_mcost;
     }
     __syncthreads();
   }
-  if (tid == 0) { jmhip_bipred_result o; o.mv[0] = (int16_t)s_mv[0]; o.mv[1] = (int16_t)s_mv[1]; o.cost = s_min; res[blockIdx.x] = o; }
+}
+
+__global__ __launch_bounds__(256) void bipred_kernel(BiDev B, const jmhip_bipred_job *__restrict__ jobs, jmhip_bipred_result *__restrict__ res)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ __attribute__((aligned(16))) BiLds L;
+  const jmhip_bipred_job job = jobs[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int ox = job.mb_x * 16, oy = job.mb_y * 16;
+  const BiCall q = {job.ref1, job.ref2, job.s_mv[0], job.s_mv[1], job.pred1[0], job.pred1[1], job.pred2[0], job.pred2[1]};
+  bi_stage_cur(B, L, ox, oy);
+  if (job.stage == 0) {
+    const unsigned k = bi_fullpel(B, L, smem, ox, oy, q, job.mv[0], job.mv[1], job.search_range);
+    if (tid == 0) {
+      int mvx = job.mv[0], mvy = job.mv[1];
+      jmhip_bipred_result o;
+      o.cost = bi_fullpel_accept(k, job.min_mcost, &mvx, &mvy);
+      o.mv[0] = (int16_t)mvx; o.mv[1] = (int16_t)mvy;
+      res[blockIdx.x] = o;
+    }
+    return;
+  }
+  if (tid == 0) { L.swept[0] = job.mv[0]; L.swept[1] = job.mv[1]; L.min_mcost = job.min_mcost; }
+  bi_subpel(B, L, ox, oy, q);
+  if (tid == 0) { jmhip_bipred_result o; o.mv[0] = (int16_t)L.swept[0]; o.mv[1] = (int16_t)L.swept[1]; o.cost = L.min_mcost; res[blockIdx.x] = o; }
+}
+
+// The bi-predictive refinement chain of BlockMotionSearch (mv-search.c:889-1022, SearchMode -1 / 0) for one 16x16 block: refinements + 1
+// integer searches that alternate the lists, then up to two sub-pel refinements. One workgroup runs all of it: the current block stays in
+// LDS, every integer step stages its own window and fixed block, thread 0 keeps the chain's books in LDS between barriers and writes the
+// trace into the result record, which leaves LDS once at the end. Side "a" is `list` (fixed in even steps), "b" is list ^ 1.
+// (waves_per_eu 3: the compiler's own allocation is 171 registers, three over the step to three workgroups per CU, the residency bipred_kernel has; no scratch)
+struct BiChain { int refinements, search_range, subpel; };
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void bipred_chain_kernel(BiDev B, BiChain C, const jmhip_bipred_chain_job *__restrict__ jobs, jmhip_bipred_chain_result *__restrict__ res)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ __attribute__((aligned(16))) BiLds L;
+  __shared__ __attribute__((aligned(16))) jmhip_bipred_chain_result s_res;
+  __shared__ int s_fixed[2], s_min;                  // tempmv and min_mcostbi; bimv (the swept vector) lives in L.swept
+  static_assert(sizeof(jmhip_bipred_chain_result) % 4 == 0, "the record leaves LDS as 32-bit words");
+  const jmhip_bipred_chain_job job = jobs[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int ox = job.mb_x * 16, oy = job.mb_y * 16;
+  bi_stage_cur(B, L, ox, oy);
+  if (tid == 0) {
+    s_fixed[0] = job.s_mv[0]; s_fixed[1] = job.s_mv[1]; L.swept[0] = job.mv[0]; L.swept[1] = job.mv[1];   // :915-926
+    s_min = 0x7fffffff;                                                                                  // :867
+  }
+  for (int k = tid; k < (int)(sizeof(s_res) / 4); k += 256) reinterpret_cast<uint32_t *>(&s_res)[k] = 0u;
+  __syncthreads();
+  // a step of parity 1 runs with iterlist = list ^ 1: pictures, predictors and weights change sides (:891-930, me_fullsearch.c:204-225)
+  auto side = [&](int odd, BiDev &Bs, BiCall &q) {
+    Bs = B;
+    if (odd) { Bs.w1 = B.w2; Bs.w2 = B.w1; }
+    q.ref1 = odd ? job.slot_b : job.slot_a; q.ref2 = odd ? job.slot_a : job.slot_b;
+    q.p1x = odd ? job.pred_b[0] : job.pred_a[0]; q.p1y = odd ? job.pred_b[1] : job.pred_a[1];
+    q.p2x = odd ? job.pred_a[0] : job.pred_b[0]; q.p2y = odd ? job.pred_a[1] : job.pred_b[1];
+  };
+  for (int i = 0; i <= C.refinements; i++) {
+    BiDev Bs; BiCall q;
+    side(i & 1, Bs, q);
+    q.smvx = s_fixed[0]; q.smvy = s_fixed[1];
+    const int cx = L.swept[0], cy = L.swept[1];
+    const unsigned key = bi_fullpel(Bs, L, smem, ox, oy, q, cx, cy, C.search_range >> i);
+    if (tid == 0) {
+      int mvx = cx, mvy = cy;
+      const int min_in = s_min, cost = bi_fullpel_accept(key, min_in, &mvx, &mvy);
+      s_res.step_smv[i][0] = (int16_t)q.smvx; s_res.step_smv[i][1] = (int16_t)q.smvy;
+      s_res.step_mv_in[i][0] = (int16_t)cx; s_res.step_mv_in[i][1] = (int16_t)cy;
+      s_res.step_mv_out[i][0] = (int16_t)mvx; s_res.step_mv_out[i][1] = (int16_t)mvy;
+      s_res.step_min_in[i] = min_in; s_res.step_cost[i] = cost;
+      s_min = cost;
+      if (i < C.refinements) { L.swept[0] = q.smvx; L.swept[1] = q.smvy; s_fixed[0] = mvx; s_fixed[1] = mvy; }   // the next step's swap, :895-898 / :908-911
+      else { L.swept[0] = mvx; L.swept[1] = mvy; }
+    }
+    __syncthreads();
+  }
+  const int last = C.refinements & 1;
+  int n = C.refinements + 1;
+  if (tid == 0) {                                    // quarter-pel units, :978-981
+    s_fixed[0] <<= 2; s_fixed[1] <<= 2; L.swept[0] <<= 2; L.swept[1] <<= 2;
+    if (C.subpel >= 1) s_min = 0x7fffffff;           // start_me_refinement_hp == 0, :986-989
+  }
+  __syncthreads();
+  for (int s = 0; s < C.subpel; s++, n++) {
+    // first call (:998): list = iterlist, refines bimv with mv fixed; second (:1018): the roles exchanged, the minimum carried
+    BiDev Bs; BiCall q;
+    side(last ^ s, Bs, q);
+    q.smvx = s_fixed[0]; q.smvy = s_fixed[1];
+    const int cx = L.swept[0], cy = L.swept[1];
+    if (tid == 0) {
+      s_res.step_smv[n][0] = (int16_t)q.smvx; s_res.step_smv[n][1] = (int16_t)q.smvy;
+      s_res.step_mv_in[n][0] = (int16_t)cx; s_res.step_mv_in[n][1] = (int16_t)cy;
+      s_res.step_min_in[n] = s_min;
+      L.min_mcost = s_min;
+    }
+    bi_subpel(Bs, L, ox, oy, q);
+    if (tid == 0) {
+      const int mvx = L.swept[0], mvy = L.swept[1];
+      s_res.step_mv_out[n][0] = (int16_t)mvx; s_res.step_mv_out[n][1] = (int16_t)mvy;
+      s_res.step_cost[n] = L.min_mcost;
+      s_min = L.min_mcost;
+      L.swept[0] = q.smvx; L.swept[1] = q.smvy; s_fixed[0] = mvx; s_fixed[1] = mvy;   // exchange the roles for the second call
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    // after an odd number of sub-pel calls the cells hold the pair exchanged: mv is the vector on iterlist, bimv the one on iterlist ^ 1 (:1028-1031)
+    const int sw = C.subpel & 1;
+    s_res.mv[0] = (int16_t)(sw ? L.swept[0] : s_fixed[0]); s_res.mv[1] = (int16_t)(sw ? L.swept[1] : s_fixed[1]);
+    s_res.bimv[0] = (int16_t)(sw ? s_fixed[0] : L.swept[0]); s_res.bimv[1] = (int16_t)(sw ? s_fixed[1] : L.swept[1]);
+    s_res.iterlist_swapped = (int16_t)last; s_res.n_steps = (int16_t)n; s_res.cost = s_min;
+  }
+  __syncthreads();
+  uint32_t *o = reinterpret_cast<uint32_t *>(res + blockIdx.x);
+  for (int k = tid; k < (int)(sizeof(s_res) / 4); k += 256) o[k] = reinterpret_cast<const uint32_t *>(&s_res)[k];
 }
 
 }  // namespace
@@ -509,6 +642,54 @@ extern "C" int jmhip_bipred_search(jmhip_ctx *c, const jmhip_bipred_params *prm,
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(dj); (void)hipFree(dr);
   if (e != hipSuccess) { c->err = std::string("jmhip_bipred_search: ") + hipGetErrorString(e); return JMHIP_ERR_DEVICE; }
+  return JMHIP_OK;
+}
+
+extern "C" int jmhip_bipred_chain(jmhip_ctx *c, const jmhip_bipred_chain_params *prm, const jmhip_bipred_chain_job *jobs, int n, jmhip_bipred_chain_result *results)
+{
+  if (!c || !prm || !jobs || !results || n <= 0) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: NULL/empty arguments") : JMHIP_ERR_ARG;
+  if (!c->has_cur) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: current picture not uploaded");
+  if (prm->refinements < 0 || prm->refinements > 5 || prm->subpel < 0 || prm->subpel > 2) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: refinements (0..5) / subpel (0..2)");
+  if (prm->search_range < 0) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: search range");
+  if (prm->search_range > 44) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_chain: search range > 44");
+  for (int i = 0; i < n; i++) {
+    const jmhip_bipred_chain_job &j = jobs[i];
+    if (j.mb_x < 0 || j.mb_x >= c->mbw || j.mb_y < 0 || j.mb_y >= c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: macroblock outside the picture");
+    for (int k = 0; k < 2; k++) {
+      const int s = k ? j.slot_b : j.slot_a;
+      if (s < 0 || s >= (int)c->refs.size() || !c->refs[s].has_pic || (prm->subpel > 0 && !c->refs[s].has_luma_sub))
+        return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: reference slot not ready");
+    }
+    // pel units: the chain moves a vector by less than 2 * search_range, and the quarter-pel results must fit 16 bits
+    for (int k = 0; k < 2; k++) if (j.mv[k] < -4096 || j.mv[k] > 4096 || j.s_mv[k] < -4096 || j.s_mv[k] > 4096) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: vector out of range");
+  }
+  for (int k = 0; k < 3; k++) if (prm->lambda[k] < 0 || prm->lambda[k] > 4000000) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_chain: lambda factor out of the packed key range");
+  if (prm->apply_weights && (prm->luma_log_weight_denom < 0 || prm->luma_log_weight_denom > 14)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: weight denominator");
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  int rc = jm_ensure_ref_table(c);
+  if (rc) return rc;
+  if (c->bic_cap < (size_t)n) {
+    if (c->bic_jobs_dev) JM_HIP_CHECK(c, hipFree(c->bic_jobs_dev));
+    if (c->bic_res_dev) JM_HIP_CHECK(c, hipFree(c->bic_res_dev));
+    c->bic_jobs_dev = c->bic_res_dev = nullptr; c->bic_cap = 0;
+    if (hipMalloc(&c->bic_jobs_dev, sizeof(jmhip_bipred_chain_job) * (size_t)n) != hipSuccess || hipMalloc(&c->bic_res_dev, sizeof(jmhip_bipred_chain_result) * (size_t)n) != hipSuccess)
+      return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred chain arrays");
+    c->bic_cap = (size_t)n;
+  }
+  BiDev B{};
+  B.W = c->W; B.H = c->H; B.Wp = c->Wp; B.Hp = c->Hp; B.cur = c->cur_y;
+  B.lam_f = prm->lambda[0]; B.lam_h = prm->lambda[1]; B.lam_q = prm->lambda[2]; B.t8x8 = prm->transform8x8_mode ? 1 : 0;
+  B.wp = prm->apply_weights ? 1 : 0; B.w1 = prm->weight_a; B.w2 = prm->weight_b; B.off = prm->offset_bi; B.rnd = prm->wp_luma_round; B.den = prm->luma_log_weight_denom;
+  B.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
+  B.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
+  const BiChain C = {prm->refinements, prm->search_range, prm->subpel};
+  const int UW = 2 * prm->search_range + 1, pitch = (UW + 15 + 3 + 4) & ~3;      // step 0 has the largest window
+  const size_t lds = (size_t)pitch * (UW + 15) + 16;
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->bic_jobs_dev, jobs, sizeof(jmhip_bipred_chain_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  bipred_chain_kernel<<<n, 256, lds, c->stream>>>(B, C, (const jmhip_bipred_chain_job *)c->bic_jobs_dev, (jmhip_bipred_chain_result *)c->bic_res_dev);
+  JM_HIP_CHECK(c, hipGetLastError());
+  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->bic_res_dev, sizeof(jmhip_bipred_chain_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
 

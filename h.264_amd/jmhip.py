@@ -74,6 +74,20 @@ class BipredParams(C.Structure):
                 ("offset_bi", C.c_int), ("wp_luma_round", C.c_int), ("luma_log_weight_denom", C.c_int)]
 
 
+# jmhip_bipred_chain: the job is the argument list of the chain's first FullPelBlockMotionBiPred call, the result the final pair and a per-step trace
+BIPRED_CHAIN_JOB_DTYPE = np.dtype([("mb_x", "<i2"), ("mb_y", "<i2"), ("slot_a", "<i2"), ("slot_b", "<i2"), ("s_mv", "<i2", (2,)), ("mv", "<i2", (2,)),
+                                   ("pred_a", "<i2", (2,)), ("pred_b", "<i2", (2,))])
+BIPRED_CHAIN_RESULT_DTYPE = np.dtype([("mv", "<i2", (2,)), ("bimv", "<i2", (2,)), ("iterlist_swapped", "<i2"), ("n_steps", "<i2"), ("cost", "<i4"),
+                                      ("step_smv", "<i2", (8, 2)), ("step_mv_in", "<i2", (8, 2)), ("step_mv_out", "<i2", (8, 2)),
+                                      ("step_min_in", "<i4", (8,)), ("step_cost", "<i4", (8,))])
+
+
+class BipredChainParams(C.Structure):
+    _fields_ = [("lambda_", C.c_int32 * 3), ("transform8x8_mode", C.c_int32), ("apply_weights", C.c_int32), ("weight_a", C.c_int32), ("weight_b", C.c_int32),
+                ("offset_bi", C.c_int32), ("wp_luma_round", C.c_int32), ("luma_log_weight_denom", C.c_int32),
+                ("refinements", C.c_int32), ("search_range", C.c_int32), ("subpel", C.c_int32)]
+
+
 SLICE_REFS = 5
 
 
@@ -191,6 +205,7 @@ def load_library():
     lib.jmhip_me_subpel.argtypes = [vp, C.POINTER(MeParams), vp, ip, vp]
     lib.jmhip_distortion_surface.argtypes = [vp, ip, vp, ip, vp]
     lib.jmhip_bipred_search.argtypes = [vp, C.POINTER(BipredParams), vp, ip, vp]
+    lib.jmhip_bipred_chain.argtypes = [vp, C.POINTER(BipredChainParams), vp, ip, vp]
     lib.jmhip_tq_batch.argtypes = [vp, ip, ip, vp, ip, vp, ip, vp]
     lib.jmhip_flat_quant.argtypes = [vp, ip, ip, ip]
     lib.jmhip_flat_quant.restype = None
@@ -242,11 +257,13 @@ def load_library():
     lib.jmhip_frame_bipred_set.argtypes = [vp, vp, ip, vp]
     for which, dt in ((0, ME_MB_DTYPE), (1, ME_RESULT_DTYPE), (2, QUANT_DTYPE), (3, TQ_JOB_DTYPE), (4, TQ_RESULT_DTYPE),
                       (5, DIST_JOB_DTYPE), (8, MB_MODE_DTYPE), (9, SURFACE_JOB_DTYPE), (10, BIPRED_JOB_DTYPE), (11, BIPRED_RESULT_DTYPE), (13, PREDCOST_JOB_DTYPE),
-                      (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE), (24, MB_RESIDUAL422_DTYPE)):
+                      (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE), (24, MB_RESIDUAL422_DTYPE),
+                      (30, BIPRED_CHAIN_JOB_DTYPE), (32, BIPRED_CHAIN_RESULT_DTYPE)):
         if lib.jmhip_sizeof(which) != dt.itemsize:
             raise JmhipError("binding layout mismatch for struct %d: C %d vs numpy %d" % (which, lib.jmhip_sizeof(which), dt.itemsize))
     if lib.jmhip_sizeof(6) != C.sizeof(MeParams) or lib.jmhip_sizeof(7) != C.sizeof(Config) or lib.jmhip_sizeof(12) != C.sizeof(BipredParams) or \
-            lib.jmhip_sizeof(16) != C.sizeof(DeblockParams) or lib.jmhip_sizeof(17) != C.sizeof(SliceParams) or lib.jmhip_sizeof(19) != C.sizeof(FrameWp) or lib.jmhip_sizeof(20) != MB_BIPRED_DTYPE.itemsize or lib.jmhip_sizeof(22) != MB_RESIDUAL_DTYPE.itemsize or lib.jmhip_sizeof(21) != C.sizeof(FrameBw):
+            lib.jmhip_sizeof(16) != C.sizeof(DeblockParams) or lib.jmhip_sizeof(17) != C.sizeof(SliceParams) or lib.jmhip_sizeof(19) != C.sizeof(FrameWp) or lib.jmhip_sizeof(20) != MB_BIPRED_DTYPE.itemsize or lib.jmhip_sizeof(22) != MB_RESIDUAL_DTYPE.itemsize or lib.jmhip_sizeof(21) != C.sizeof(FrameBw) or \
+            lib.jmhip_sizeof(31) != C.sizeof(BipredChainParams):
         raise JmhipError("binding layout mismatch for jmhip_me_params / jmhip_config")
     _lib = lib
     return lib
@@ -535,6 +552,13 @@ class Context:
         jobs = np.ascontiguousarray(jobs, dtype=BIPRED_JOB_DTYPE)
         res = np.zeros(len(jobs), dtype=BIPRED_RESULT_DTYPE)
         self._chk(self.lib.jmhip_bipred_search(self.h, C.byref(prm), _ptr(jobs), len(jobs), _ptr(res)), "jmhip_bipred_search")
+        return res
+
+    def bipred_chain(self, prm, jobs):
+        """jmhip_bipred_chain: every job's whole refinement chain in one launch; BIPRED_CHAIN_RESULT_DTYPE records."""
+        jobs = np.ascontiguousarray(jobs, dtype=BIPRED_CHAIN_JOB_DTYPE)
+        res = np.zeros(len(jobs), dtype=BIPRED_CHAIN_RESULT_DTYPE)
+        self._chk(self.lib.jmhip_bipred_chain(self.h, C.byref(prm), _ptr(jobs), len(jobs), _ptr(res)), "jmhip_bipred_chain")
         return res
 
     def distortion_surface(self, kind, jobs):

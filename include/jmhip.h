@@ -263,6 +263,45 @@ typedef struct {
 } jmhip_bipred_params;
 int jmhip_bipred_search(jmhip_ctx *ctx, const jmhip_bipred_params *prm, const jmhip_bipred_job *jobs, int n, jmhip_bipred_result *results);
 
+/* The bi-predictive refinement chain of BlockMotionSearch (src/mv-search.c:864-1034, SearchMode -1 / 0; 16x16 block, ref == 0) in ONE launch,
+ * one workgroup per job: for i = 0 .. refinements a FullPelBlockMotionBiPred (src/me_fullsearch.c:164) of range search_range >> i that starts
+ * from the previous step's vectors and carries min_mcostbi (:889-975) -- odd steps run with iterlist = list ^ 1: the fixed block and the swept
+ * window change pictures, pred_mv1 / pred_mv2 change places (:891-930) and, under weighting, so do weight1 / weight2 (src/me_fullsearch.c:218-226;
+ * offsetBi is symmetric) --, then with subpel >= 1 SubPelBlockSearchBiPred (:520) on quarter-pel vectors from min_mcostbi = INT_MAX
+ * (start_me_refinement_hp == 0), refining bimv with mv fixed (:984-1002), and with subpel == 2 a second one with the roles exchanged and the
+ * minimum carried (start_me_refinement_qp == 1, :1004-1022). Metrics as jmhip_bipred_search: SAD at integer, Hadamard SAD at sub-pel positions.
+ * A job is the argument list of the chain's FIRST FullPelBlockMotionBiPred call (i == 0, iterlist == list); side "a" is `list`, "b" list ^ 1. */
+typedef struct {
+  int16_t mb_x, mb_y;
+  int16_t slot_a, slot_b;          /* reference slots of listX[list][0] (fixed in even steps) and listX[list ^ 1][0]               */
+  int16_t s_mv[2], mv[2];          /* pel units: the uni-directional result (tempmv) and the first centre (bimv), :915-926         */
+  int16_t pred_a[2], pred_b[2];    /* quarter-pel: pred_mv of `list`, pred_mv_bi of the other list (:880)                          */
+} jmhip_bipred_chain_job;
+typedef struct {
+  int32_t lambda[3];               /* lambda_factor[F_PEL, H_PEL, Q_PEL]                                                           */
+  int32_t transform8x8_mode;       /* 8x8 Hadamard in the sub-pel calls (test8x8transform for block type 1)                        */
+  int32_t apply_weights;           /* active_pps->weighted_bipred_idc > 0                                                          */
+  int32_t weight_a, weight_b;      /* weight1 / weight2 of the FIRST call: wbp_weight of `list` and of list ^ 1                    */
+  int32_t offset_bi, wp_luma_round, luma_log_weight_denom;
+  int32_t refinements;             /* input->BiPredMERefinements, 0..5 (src/configfile.h:178)                                      */
+  int32_t search_range;            /* input->BiPredMESearchRange, <= 44 (beyond: JMHIP_ERR_UNSUPPORTED)                            */
+  int32_t subpel;                  /* input->BiPredMESubPel, 0 when input->DisableSubpelME (:984): 0..2                            */
+} jmhip_bipred_chain_params;
+typedef struct {
+  int16_t mv[2], bimv[2];          /* quarter-pel (pel << 2 when subpel == 0), as written to bipred_mv[..][iterlist] / [iterlist ^ 1], :1028-1031 */
+  int16_t iterlist_swapped;        /* 1 when the last integer step ran with list ^ 1 (refinements odd): iterlist at :1028          */
+  int16_t n_steps;                 /* refinements + 1 + subpel                                                                     */
+  int32_t cost;                    /* min_mcostbi at the end                                                                       */
+  /* The trace a per-call binding answers from. Step k < refinements + 1 is the k-th FullPelBlockMotionBiPred call (pel units, list ^ (k & 1)),
+   * the steps after it the SubPelBlockSearchBiPred calls (quarter-pel): the *s_mv, *mv and min_mcost JM passes, the *mv and the return value
+   * it gets back. Steps from n_steps on are zero. */
+  int16_t step_smv[8][2], step_mv_in[8][2], step_mv_out[8][2];
+  int32_t step_min_in[8], step_cost[8];
+} jmhip_bipred_chain_result;
+/* jobs / results: host arrays of n entries; the device arrays belong to the context and grow on demand. The call synchronises. */
+int jmhip_bipred_chain(jmhip_ctx *ctx, const jmhip_bipred_chain_params *prm, const jmhip_bipred_chain_job *jobs, int n,
+                       jmhip_bipred_chain_result *results);
+
 /* SubPelBlockMotionSearch alone (src/me_fullsearch.c:341): results[i].mv_int[p] is the INPUT (integer vector in pel
  * units, as FullPel/FastFull left it), results[i].mv/cost[p] the output. Same params/jobs as jmhip_me_frame. With
  * metric_set and equal metrics at the integer and half-pel level, results[i].cost_int[p] is an input too: the min_mcost the
@@ -698,7 +737,8 @@ int jmhip_ref_unpack_bands(jmhip_ctx *ctx, int ref, const void *chunks_device, i
  * 2 jmhip_quant, 3 jmhip_tq_job, 4 jmhip_tq_result, 5 jmhip_dist_job, 6 jmhip_me_params, 7 jmhip_config,
  * 8 jmhip_mb_mode, 9 jmhip_surface_job, 10 jmhip_bipred_job, 11 jmhip_bipred_result, 12 jmhip_bipred_params, 13 jmhip_predcost_job,
  * 14 jmhip_deblock_mb, 15 jmhip_deblock_blk, 16 jmhip_deblock_params, 17 jmhip_slice_params, 18 jmhip_mb_inter, 19 jmhip_frame_wp,
- * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8, 24 jmhip_mb_residual422. */
+ * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8, 24 jmhip_mb_residual422 (25..29: none, -1),
+ * 30 jmhip_bipred_chain_job, 31 jmhip_bipred_chain_params, 32 jmhip_bipred_chain_result. */
 int jmhip_sizeof(int which);
 
 /* Flat (no scaling matrix) tables: CalculateQuantParam / CalculateQuant8Param (src/q_matrix.c:451,590) and

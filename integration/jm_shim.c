@@ -31,6 +31,10 @@
  *        three passes per slice in JM's order -- the 8x8-transform P8x8 candidate (src/md_low.c:226-251, jmhip_slice_to_frame_candidates8), the
  *        4x4-transform P8x8 candidate (:254-273, Transform8x8Mode 1 only) and the decision -- and dct_8x8 calls are answered from the 8x8 lists
  *        (jmhip_mb_residual8) of the pass whose prediction JM works on, with the same checks as dct_4x4.
+ * 0x20000 (with 0x200; opt-in) the bi-predictive refinement chain of a B macroblock (src/mv-search.c:889-1022) as ONE launch: the chain's first
+ *        FullPelBlockMotionBiPred call runs jmhip_bipred_chain, and the following FullPelBlockMotionBiPred / SubPelBlockSearchBiPred calls of
+ *        the same macroblock and list are answered from its trace after checking that JM passes the recorded inputs; on a mismatch the trace
+ *        is dropped and the call takes the per-call device path.
  * 0x8000 the sub-pel planes stay on the device until JM is about to read them: getSubImagesLuma / getSubImagesChroma still upload the finished picture
  *        and build the planes, but only the integer plane (which JM's weighted-prediction estimation reads) crosses back at once; the other planes
  *        of a picture are fetched into JM's rows the first time a call is FORWARDED to JM code that reads reference planes (JM's own
@@ -67,14 +71,15 @@ extern const int LEVELMVLIMIT[17][6];
 extern int *mvbits;                       /* src/mv-search.c:59 */
 
 enum { S_LUMA, S_CHROMA, S_FULL, S_SUB, S_FAST, S_D4, S_D8, S_D16, S_DCR, S_WALK, S_SAD, S_SATD, S_BIFULL, S_BISUB, S_TDEC, S_SKIPC, S_BIDC, S_DEBLOCK, S_SLICE, S_BMS,
-       S_FRAME, S_D4R, S_DCRR, S_LPRED, S_CPRED, S_LAZY, S_D8R, S_LPREDC, S_COUNT };
+       S_FRAME, S_D4R, S_DCRR, S_LPRED, S_CPRED, S_LAZY, S_D8R, S_LPREDC, S_CHAIN, S_CHAINC, S_COUNT };
 static const char *s_names[S_COUNT] = { "getSubImagesLuma", "getSubImagesChroma", "FullPelBlockMotionSearch",
   "SubPelBlockMotionSearch", "FastFullPelBlockMotionSearch", "dct_4x4", "dct_8x8", "dct_16x16", "dct_chroma",
   "EPZS_UMHex_integer_walks", "computeSAD", "computeSATD", "FullPelBlockMotionBiPred", "SubPelBlockSearchBiPred",
   "TransformDecision", "GetSkipCostMB", "BIDPartitionCost", "DeblockFrame",
   "P slices (one device call each)", "BlockMotionSearch",
   "frame stage of P slices", "dct_4x4 (slice records)", "dct_chroma (slice records)", "LumaPrediction (slice)", "ChromaPrediction4x4 (slice)", "sub-pel planes fetched on demand",
-  "dct_8x8 (slice records)", "LumaPrediction (mode decision costs)" };
+  "dct_8x8 (slice records)", "LumaPrediction (mode decision costs)",
+  "bi-pred chain", "bi-pred calls (chain)" };         /* chains run / dropped on a mismatch; calls answered from a chain's trace */
 static long n_dev[S_COUNT], n_fwd[S_COUNT];
 static double t_dev[S_COUNT], t_last[S_COUNT];             /* JMHIP_SHIM_STATS: wall seconds inside the coarse device-side hooks (planes, slice search, loop filter) */
 static int stats_on;
@@ -562,6 +567,39 @@ static int bipred_ok(short ref, int list, int blocktype, int *slot1, int *slot2,
   return 1;
 }
 
+/* The refinement chain (mask 0x20000). A chain is a pure function of its first call's arguments and the slice's settings (src/mv-search.c:889-1022):
+ * step k <= BiPredMERefinements is the k-th FullPelBlockMotionBiPred call (list ^ (k & 1), range >> k), the steps after it the SubPelBlockSearchBiPred
+ * calls. bms_lambda: lambda_factor[] of the running BlockMotionSearch, whose sub-pel entries the first call does not receive. */
+static int bms_lambda[3];
+static struct { int on, next, mb_nr, list, pix_x, pix_y; jmhip_bipred_chain_params prm; jmhip_bipred_chain_job job; jmhip_bipred_chain_result r; } bc;
+
+static int chain_subpel(void) { return (input->BiPredMESubPel && !input->DisableSubpelME) ? (input->BiPredMESubPel == 2 ? 2 : 1) : 0; }
+
+/* is this call step bc.next of the running chain, with the inputs the device assumed? pred: of the swept vector; pred_fixed: NULL in the sub-pel calls */
+static int chain_step_matches(int subpel_call, short ref, int list, int pic_pix_x, int pic_pix_y, const short *pred_fixed, const short *pred,
+                              const short *mv, const short *s_mv, int search_range, int min_mcost, const int *lam3)
+{
+  const int k = bc.next, nint = bc.prm.refinements + 1;
+  const int odd = k < nint ? (k & 1) : ((bc.prm.refinements & 1) ^ (k - nint));
+  const int16_t *pf = odd ? bc.job.pred_b : bc.job.pred_a, *ps = odd ? bc.job.pred_a : bc.job.pred_b;
+  if (!bc.on || k >= bc.r.n_steps || subpel_call != (k >= nint) || ref != 0 || img->current_mb_nr != bc.mb_nr || pic_pix_x != bc.pix_x || pic_pix_y != bc.pix_y) return 0;
+  if (list != (bc.list ^ odd) || s_mv[0] != bc.r.step_smv[k][0] || s_mv[1] != bc.r.step_smv[k][1] || mv[0] != bc.r.step_mv_in[k][0] || mv[1] != bc.r.step_mv_in[k][1]) return 0;
+  if (pred[0] != ps[0] || pred[1] != ps[1] || min_mcost != bc.r.step_min_in[k]) return 0;
+  if (subpel_call) return lam3[1] == bc.prm.lambda[1] && lam3[2] == bc.prm.lambda[2];
+  return pred_fixed[0] == pf[0] && pred_fixed[1] == pf[1] && search_range == (bc.prm.search_range >> k) && lam3[0] == bc.prm.lambda[0];
+}
+
+static int chain_answer(short *mv_x, short *mv_y)
+{
+  const int k = bc.next++;
+  *mv_x = bc.r.step_mv_out[k][0]; *mv_y = bc.r.step_mv_out[k][1];
+  if (bc.next >= bc.r.n_steps) bc.on = 0;
+  n_dev[S_CHAINC]++;
+  return bc.r.step_cost[k];
+}
+
+static void chain_drop(void) { if (bc.on) { bc.on = 0; n_fwd[S_CHAIN]++; } }
+
 int FullPelBlockMotionBiPred(imgpel *orig_pic, short ref, int list, int pic_pix_x, int pic_pix_y, int blocktype,
                              short pred_mv_x1, short pred_mv_y1, short pred_mv_x2, short pred_mv_y2,
                              short *mv_x, short *mv_y, short *s_mv_x, short *s_mv_y, int search_range, int min_mcost, int lambda_factor)
@@ -572,8 +610,31 @@ int FullPelBlockMotionBiPred(imgpel *orig_pic, short ref, int list, int pic_pix_
   lam3[0] = lambda_factor; lam3[1] = lam3[2] = 0;
   if (search_range > 44 || pic_pix_x != img->opix_x || pic_pix_y != img->opix_y || !bipred_ok(ref, list, blocktype, &s1, &s2, &prm, lam3)) {
     if (!orig) orig = next_sym("FullPelBlockMotionBiPred");
+    chain_drop();
     n_fwd[S_BIFULL]++;
     return orig(orig_pic, ref, list, pic_pix_x, pic_pix_y, blocktype, pred_mv_x1, pred_mv_y1, pred_mv_x2, pred_mv_y2, mv_x, mv_y, s_mv_x, s_mv_y, search_range, min_mcost, lambda_factor);
+  }
+  if (shim_mask & 0x20000) {
+    const short pf[2] = { pred_mv_x1, pred_mv_y1 }, ps[2] = { pred_mv_x2, pred_mv_y2 }, mv[2] = { *mv_x, *mv_y }, smv[2] = { *s_mv_x, *s_mv_y };
+    if (bc.on && chain_step_matches(0, ref, list, pic_pix_x, pic_pix_y, pf, ps, mv, smv, search_range, min_mcost, lam3)) return chain_answer(mv_x, mv_y);
+    chain_drop();
+    /* the chain's first call: min_mcostbi is still max_value (:867) and the range is the configured one (:964 with i == 0) */
+    if (ref == 0 && min_mcost == INT_MAX && search_range == input->BiPredMESearchRange && input->BiPredMERefinements >= 0 && input->BiPredMERefinements <= 5 &&
+        lambda_factor == bms_lambda[0] && abs(mv[0]) <= 4096 && abs(mv[1]) <= 4096 && abs(smv[0]) <= 4096 && abs(smv[1]) <= 4096) {
+      memset(&bc, 0, sizeof(bc));
+      bc.prm.lambda[0] = bms_lambda[0]; bc.prm.lambda[1] = bms_lambda[1]; bc.prm.lambda[2] = bms_lambda[2];
+      bc.prm.transform8x8_mode = prm.transform8x8_mode; bc.prm.apply_weights = prm.apply_weights;
+      bc.prm.weight_a = prm.weight1; bc.prm.weight_b = prm.weight2; bc.prm.offset_bi = prm.offset_bi;
+      bc.prm.wp_luma_round = prm.wp_luma_round; bc.prm.luma_log_weight_denom = prm.luma_log_weight_denom;
+      bc.prm.refinements = input->BiPredMERefinements; bc.prm.search_range = search_range; bc.prm.subpel = chain_subpel();
+      bc.job.mb_x = pic_pix_x >> 4; bc.job.mb_y = pic_pix_y >> 4; bc.job.slot_a = s1; bc.job.slot_b = s2;
+      bc.job.s_mv[0] = smv[0]; bc.job.s_mv[1] = smv[1]; bc.job.mv[0] = mv[0]; bc.job.mv[1] = mv[1];
+      bc.job.pred_a[0] = pf[0]; bc.job.pred_a[1] = pf[1]; bc.job.pred_b[0] = ps[0]; bc.job.pred_b[1] = ps[1];
+      OK(jmhip_bipred_chain(g, &bc.prm, &bc.job, 1, &bc.r));
+      bc.on = 1; bc.next = 0; bc.mb_nr = img->current_mb_nr; bc.list = list; bc.pix_x = pic_pix_x; bc.pix_y = pic_pix_y;
+      n_dev[S_CHAIN]++;
+      return chain_answer(mv_x, mv_y);
+    }
   }
   memset(&job, 0, sizeof(job));
   job.mb_x = pic_pix_x >> 4; job.mb_y = pic_pix_y >> 4; job.ref1 = s1; job.ref2 = s2;
@@ -596,8 +657,14 @@ int SubPelBlockSearchBiPred(imgpel *orig_pic, short ref, int list, int pic_pix_x
   if (search_pos2 != 9 || search_pos4 != 9 || pic_pix_x != img->opix_x || pic_pix_y != img->opix_y ||
       !bipred_ok(ref, list, blocktype, &s1, &s2, &prm, lambda)) {
     if (!orig) orig = next_sym("SubPelBlockSearchBiPred");
+    chain_drop();
     n_fwd[S_BISUB]++;
     return orig(orig_pic, ref, list, pic_pix_x, pic_pix_y, blocktype, pred_mv_x, pred_mv_y, mv_x, mv_y, s_mv_x, s_mv_y, search_pos2, search_pos4, min_mcost, lambda);
+  }
+  if (shim_mask & 0x20000) {
+    const short ps[2] = { pred_mv_x, pred_mv_y }, mv[2] = { *mv_x, *mv_y }, smv[2] = { *s_mv_x, *s_mv_y };
+    if (bc.on && chain_step_matches(1, ref, list, pic_pix_x, pic_pix_y, NULL, ps, mv, smv, 0, min_mcost, lambda)) return chain_answer(mv_x, mv_y);
+    chain_drop();
   }
   memset(&job, 0, sizeof(job));
   job.mb_x = pic_pix_x >> 4; job.mb_y = pic_pix_y >> 4; job.ref1 = s1; job.ref2 = s2;
@@ -1531,7 +1598,9 @@ static long sl_passes(void) { return sl.passes; }
 int BlockMotionSearch(short ref, int list, int mb_x, int mb_y, int blocktype, int search_range, int *lambda_factor)
 {
   static int (*orig)(short, int, int, int, int, int, int *);
-  int covered = slice_mode_covered() && img->type == P_SLICE && list == 0 && img->structure == FRAME && !img->MbaffFrameFlag && ctx_ready() && cur_ready() &&
+  int covered;
+  bms_lambda[0] = lambda_factor[0]; bms_lambda[1] = lambda_factor[1]; bms_lambda[2] = lambda_factor[2];   /* for the bi-pred chain this call may start */
+  covered = slice_mode_covered() && img->type == P_SLICE && list == 0 && img->structure == FRAME && !img->MbaffFrameFlag && ctx_ready() && cur_ready() &&
                 listXsize[LIST_0] <= JMHIP_SLICE_REFS;
   if (!covered) {
     if (!orig) orig = next_sym("BlockMotionSearch");
