@@ -566,12 +566,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void b
   }
   __syncthreads();
   for (int s = 0; s < C.subpel; s++, n++) {
-    // first call (:998): list = iterlist, refines bimv with mv fixed; second (:1018): the roles exchanged, the minimum carried
+    // first call (:998): list = iterlist, refines bimv with mv fixed; second (:1018): the roles exchanged, and the minimum starts over as well:
+    // :1006 resets it when EITHER start_me_refinement_hp or _qp is 0, and _hp is 0 under this kernel's metrics (SAD integer, Hadamard sub-pel)
     BiDev Bs; BiCall q;
     side(last ^ s, Bs, q);
     q.smvx = s_fixed[0]; q.smvy = s_fixed[1];
     const int cx = L.swept[0], cy = L.swept[1];
     if (tid == 0) {
+      if (s == 1) s_min = 0x7fffffff;                // :1006-1009
       s_res.step_smv[n][0] = (int16_t)q.smvx; s_res.step_smv[n][1] = (int16_t)q.smvy;
       s_res.step_mv_in[n][0] = (int16_t)cx; s_res.step_mv_in[n][1] = (int16_t)cy;
       s_res.step_min_in[n] = s_min;

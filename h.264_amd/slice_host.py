@@ -8,9 +8,10 @@ QP_N = 28
 
 
 def slice_params(mode, R, nref, lambda_mf, ref_cost1, W, mb_first=0, mb_count=None, H=None, metric=(0, 2, 2), qp_n=QP_N, full_search=2,
-                 t8=0, t8_qp=None, cavlc=1, rdopt=0, md_metric=2):
+                 t8=0, t8_qp=None, cavlc=1, rdopt=0, md_metric=2, q8=None):
     """SearchMode `mode`, range R, `nref` list-0 references in slots 0..nref-1, every inter mode enabled, JM's default EPZS / UMHexagonS settings
-    (jmhip_epzs_setup / jmhip_umhex_setup); t8: Transform8x8Mode with the flat inter 8x8 luma quantiser at t8_qp (jmhip_flat_quant)."""
+    (jmhip_epzs_setup / jmhip_umhex_setup); t8: Transform8x8Mode with the flat inter 8x8 luma quantiser at t8_qp (jmhip_flat_quant), or with the
+    tables of the QUANT_DTYPE record q8 (scaling matrices, per-position offsets) at its qp."""
     lib = jmhip.load_library()
     p = jmhip.SliceParams()
     p.search_mode, p.search_range, p.full_search, p.num_refs = mode, R, full_search, nref
@@ -28,8 +29,8 @@ def slice_params(mode, R, nref, lambda_mf, ref_cost1, W, mb_first=0, mb_count=No
     lib.jmhip_epzs_setup(p, R, 2, 3, 2, 1, 1, 1, 0, 1, 2, 2)
     lib.jmhip_umhex_setup(p, 1, 3, qp_n, W)
     if t8:                                           # Transform8x8Mode: the inter 8x8 luma quantiser of the slice (flat matrices, default offsets)
-        qp = qp_n if t8_qp is None else t8_qp
-        q = jmhip.flat_quant(qp, 342, True)
+        qp = int(q8["qp"]) if q8 is not None else qp_n if t8_qp is None else t8_qp
+        q = q8 if q8 is not None else jmhip.flat_quant(qp, 342, True)
         p.transform8x8_mode, p.t8_qp, p.t8_cavlc, p.t8_disthres = t8, qp, cavlc, 0
         for k in range(64):
             p.t8_levelscale[k], p.t8_leveloffset[k] = int(q["levelscale"][k]), int(q["leveloffset"][k])

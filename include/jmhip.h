@@ -268,8 +268,8 @@ int jmhip_bipred_search(jmhip_ctx *ctx, const jmhip_bipred_params *prm, const jm
  * from the previous step's vectors and carries min_mcostbi (:889-975) -- odd steps run with iterlist = list ^ 1: the fixed block and the swept
  * window change pictures, pred_mv1 / pred_mv2 change places (:891-930) and, under weighting, so do weight1 / weight2 (src/me_fullsearch.c:218-226;
  * offsetBi is symmetric) --, then with subpel >= 1 SubPelBlockSearchBiPred (:520) on quarter-pel vectors from min_mcostbi = INT_MAX
- * (start_me_refinement_hp == 0), refining bimv with mv fixed (:984-1002), and with subpel == 2 a second one with the roles exchanged and the
- * minimum carried (start_me_refinement_qp == 1, :1004-1022). Metrics as jmhip_bipred_search: SAD at integer, Hadamard SAD at sub-pel positions.
+ * (start_me_refinement_hp == 0), refining bimv with mv fixed (:984-1002), and with subpel == 2 a second one with the roles exchanged, again
+ * from INT_MAX (:1006 resets when either start flag is 0, :1004-1022). Metrics as jmhip_bipred_search: SAD at integer, Hadamard SAD at sub-pel positions.
  * A job is the argument list of the chain's FIRST FullPelBlockMotionBiPred call (i == 0, iterlist == list); side "a" is `list`, "b" list ^ 1. */
 typedef struct {
   int16_t mb_x, mb_y;

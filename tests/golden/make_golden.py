@@ -36,8 +36,23 @@ RUNS = {
                            "-p", "MEDistortionHPel=1", "-p", "MEDistortionQPel=0", "-p", "FramesToBeEncoded=2"], 40),
     "main_fastfull_satd_fpel": (["-d", "encoder_main.cfg", "-p", "SearchMode=0", "-p", "MEDistortionFPel=2", "-p", "MEDistortionHPel=2",
                                  "-p", "MEDistortionQPel=2", "-p", "FramesToBeEncoded=2", "-p", "NumberBFrames=0"], 40),
+    # scaling matrices AND rounding offsets per position that change under a swap of row and column (write_matrix_files: this project's own
+    # values, not the reference's bin/*.cfg): the dct records then carry LevelScale / InvLevelScale / LevelOffset tables with T != T.T, which
+    # is what tells the oracle's [j][i] from [i][j] against the real JM (tests/test_golden.py test_asymmetric_tables_fixture)
+    "high_t8_qmatrix_qoffset_asym": (["-p", "ProfileIDC=100", "-p", "Transform8x8Mode=1", "-p", "SearchRange=16", "-p", "FramesToBeEncoded=2",
+                                      "-p", "ScalingMatrixPresentFlag=1", "-p", "QmatrixFile=qm_asym.cfg", "-p", "OffsetMatrixPresentFlag=1",
+                                      "-p", "QOffsetMatrixFile=qo_asym.cfg"] + [x for i in range(8) for x in ("-p", "ScalingListPresentFlag%d=1" % i)], 64),
 }
 KINDS = {1: "luma", 2: "chroma", 3: "fullpel", 4: "subpel", 5: "fastfull", 6: "dct4", 7: "dct8", 8: "dct16", 9: "dctc"}
+
+
+def write_matrix_files(d):
+    """QmatrixFile / QOffsetMatrixFile in JM's format (src/q_matrix.c:31-49, src/q_offsets.c:23-58 name the lists), every list different and none
+    equal to its transpose; the writers are the ones tests/test_jm_shim.py encodes with."""
+    sys.path.insert(0, ROOT)
+    from tests.test_jm_shim import write_qmatrix, write_qoffsets
+    write_qmatrix(os.path.join(d, "qm_asym.cfg"), asym=True)
+    write_qoffsets(os.path.join(d, "qo_asym.cfg"))
 
 
 def parse(path):
@@ -81,6 +96,7 @@ def main():
             for f in os.listdir(REF):
                 if f.endswith(".cfg") or f.endswith(".yuv"):
                     shutil.copy(os.path.join(REF, f), d)
+            write_matrix_files(d)
             env = dict(os.environ, JM_TAP_OUT=os.path.join(d, "tap.bin"))
             subprocess.run([TAP] + args, cwd=d, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False)
             recs = parse(os.path.join(d, "tap.bin"))

@@ -693,7 +693,7 @@ BLOCKTYPE_LUT = {(0, 0): 7, (0, 1): 6, (1, 0): 5, (1, 1): 4, (1, 3): 3, (3, 1): 
 
 def lowcplx_params(search_mode, search_range, num_refs, lambda_mf, ref_cost1, W, H, epzs=None, umhex=None, full_search=2, metric=(0, 2, 2),
                    md_metric=2, valid=(1, 1, 1, 1, 1, 1, 1), frame_ctr_b=0, img_number=1, level_mv=(-511, 511), all_mv_state=None,
-                   transform8x8_mode=0, qp=28, cavlc=1, rdopt=0):
+                   transform8x8_mode=0, qp=28, cavlc=1, rdopt=0, q8=None):
     q = LowcplxParams()
     q.search_mode, q.search_range, q.num_refs, q.full_search = search_mode, search_range, num_refs, full_search
     for m in range(1, 8):
@@ -704,6 +704,8 @@ def lowcplx_params(search_mode, search_range, num_refs, lambda_mf, ref_cost1, W,
     q.transform8x8_mode = transform8x8_mode
     if transform8x8_mode:                    # the inter 8x8 luma quantiser of the slice: flat matrices, default offset (342 / 2048), no adaptive rounding
         ls, ils, lo, _ = flat_tables(qp, 342, True)
+        if q8 is not None:                   # or a record's tables (scaling matrix, per-position offsets) at its qp
+            ls, ils, lo, qp = q8["levelscale"], q8["invlevelscale"], q8["leveloffset"], int(q8["qp"])
         q._keep_q8 = QuantHolder(dict(levelscale=ls, invlevelscale=ils, leveloffset=lo, qp=qp, adaptive_rounding=0, adapt_rnd_weight=0, field_scan=0,
                                       disthres=0, max_val=255, cavlc=cavlc, img_qp=qp, transform8x8_flag=1))
         q.q8 = C.addressof(q._keep_q8.c)

@@ -80,7 +80,8 @@ def oracle_chain(rp, cur16, job, lam, t8x8, wp, refinements, R, subpel):
         min_mcostbi = INT_MAX                                                             # start_me_refinement_hp == 0, :986-989
         bimv, min_mcostbi, u = search(1, iterlist, mv, bimv, 0, min_mcostbi)              # :998-1000: refines bimv, mv fixed
         umv |= u
-    if subpel == 2:                                                                       # :1004, the minimum carried (start_me_refinement_qp == 1)
+    if subpel == 2:                                                                       # :1004
+        min_mcostbi = INT_MAX                                                             # :1006-1009: reset when EITHER start_me_refinement_hp or _qp is 0
         mv, min_mcostbi, u = search(1, iterlist ^ 1, bimv, mv, 0, min_mcostbi)            # :1018-1020: refines mv, bimv fixed
         umv |= u
     return dict(mv=mv, bimv=bimv, cost=min_mcostbi, iterlist=iterlist, steps=steps, umv=umv)   # :1028-1031

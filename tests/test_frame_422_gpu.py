@@ -11,6 +11,7 @@ import pytest
 from tests import oracle
 from tests.test_frame import synth
 from tests.test_me import lambda_factors, make_mbs
+from tests.quant_tables import scaled_quant
 from tests.test_tq import compare_lists
 
 R = 8
@@ -39,7 +40,7 @@ CASES = {
 }
 
 
-def build_inputs(pkg, *, w, h, qp, cavlc, ar, far, planes, given, t8, seed, weighted=False, bipred=False, fmt=2, qpc=None):
+def build_inputs(pkg, *, w, h, qp, cavlc, ar, far, planes, given, t8, seed, weighted=False, bipred=False, fmt=2, qpc=None, tables=False):
     """Everything a case feeds the frame stage with, drawn on the host (no device involved)."""
     rng = np.random.default_rng(seed)
     cur, ref = synth(rng, w, h, fmt)
@@ -53,6 +54,10 @@ def build_inputs(pkg, *, w, h, qp, cavlc, ar, far, planes, given, t8, seed, weig
     quants = [pkg.flat_quant(qp, 342, **kw), pkg.flat_quant(qpc, 342, **kw), pkg.flat_quant(qpc + 3, 342, **kw)]
     if t8 != "none":
         quants.append(pkg.flat_quant(qp, 342, is8x8=True, transform8x8_flag=1, **kw))
+    if tables:                                            # a scaling matrix and per-position offsets of its own for every record, none symmetric
+        quants = [scaled_quant(pkg, q, rng, False, **kw) for q in (qp, qpc, qpc + 3)]
+        if t8 != "none":
+            quants.append(scaled_quant(pkg, qp, rng, True, transform8x8_flag=1, **kw))
     quants = np.array(quants, dtype=pkg.QUANT_DTYPE)
     modes = None
     flags = np.zeros(n, bool)
@@ -297,11 +302,7 @@ def test_cases_cover_the_branches_of_dct_chroma_422(pkg):
     assert all(seen.values()), "branches the cases do not reach: %s" % [k for k, v in seen.items() if not v]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", sorted(CASES))
-def test_fused_422_frame_stage(pkg, monkeypatch, name):
-    kw = CASES[name]
-    inp = case_inputs(pkg, name)
+def run_and_check(pkg, monkeypatch, kw, inp):
     a = run_device(pkg, monkeypatch, inp, fused=True)
     b = run_device(pkg, monkeypatch, inp, fused=False)
     check_against_separate(a, b)
@@ -318,6 +319,93 @@ def test_fused_422_frame_stage(pkg, monkeypatch, name):
     for o in (a, b):
         check_download(o["got"], o["recon"], want, inp["t8"], kw["ar"])
     check_records(a["records"], a["records8"], a["pred"], want, inp["mbs"], inp["t8"], kw["ar"], kw["cavlc"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_fused_422_frame_stage(pkg, monkeypatch, name):
+    run_and_check(pkg, monkeypatch, CASES[name], case_inputs(pkg, name))
+
+
+# Scaling matrices and per-position rounding offsets, asymmetric, a set of their own for each of luma 4x4, chroma, chroma DC (qp + 3, which
+# the 4:2:2 DC path does read) and luma 8x8; the stage takes one chroma quantiser per call, so Cb and Cr share theirs.
+# qpc: synth's chroma carries a quarter of the luma's amplitude; at the luma QP its AC levels are too few for the chroma tables to show.
+TABLE_CASES = {
+    "tables_cabac_ar_t8_some": dict(w=64, h=48, qp=24, qpc=10, cavlc=0, ar=1, far=6, planes=True, given=True, t8="some", tables=True, seed=611),
+    "tables_cavlc_4x4_chosen": dict(w=64, h=48, qp=20, qpc=10, cavlc=1, ar=0, far=6, planes=False, given=False, t8="none", tables=True, seed=612),
+    "tables_tail_15_mbs": dict(w=80, h=48, qp=26, qpc=10, cavlc=1, ar=1, far=6, planes=False, given=True, t8="some", tables=True, seed=613),
+}
+
+
+def download_differences(got, recon, want, t8, ar):
+    """check_download's comparisons as the list of names that differ; got / recon: a second oracle run's "luma" / "chroma" / "recon"."""
+    gl, wl, gc, wc = got["luma"], want["luma"], got["chroma"], want["chroma"]
+    bad = []
+    for name, d in (("luma levels", lists_differ(gl["levels"], gl["runs"], wl["levels"], wl["runs"])),
+                    ("luma levels8", bool(t8.any()) and lists_differ(gl["levels8"][t8], gl["runs8"][t8], wl["levels8"][t8], wl["runs8"][t8])),
+                    ("chroma levels", lists_differ(gc["levels"][:, :8, :16], gc["runs"][:, :8, :16], wc["levels"][:, :8, :16], wc["runs"][:, :8, :16])),
+                    ("chroma dc_levels", lists_differ(gc["dc_levels"], gc["dc_runs"], wc["dc_levels"], wc["dc_runs"]))):
+        if d:
+            bad.append(name)
+    same = lambda name, a, b: None if np.array_equal(a, b) else bad.append(name)
+    same("luma coeff_cost", gl["coeff_cost"][~t8], wl["coeff_cost"][~t8])
+    same("luma coeff_cost", gl["coeff_cost"][t8][:, :4], wl["coeff_cost"][t8][:, :4])
+    same("luma recon", gl["recon"], wl["recon"])
+    same("chroma recon", gc["recon"][:, :, :8], wc["recon"][:, :, :8])
+    for f in ("ret", "cbp_blk", "cbp_clear"):
+        same("chroma %s" % f, gc[f], wc[f])
+    if ar:
+        same("luma fadjust", gl["fadjust"], wl["fadjust"])
+        same("chroma fadjust", gc["fadjust"][:, :, :8], wc["fadjust"][:, :, :8])
+    same("cbp", got["cbp"], want["cbp"])
+    same("cbp_blk", got["cbp_blk"], want["cbp_blk"])
+    for g, wv, name in zip(recon, want["recon"], "YUV"):
+        same("picture recon %s" % name, g, wv)
+    return bad
+
+
+_table_inputs = {}
+
+
+def table_inputs(pkg, name):
+    """The inputs of a TABLE_CASES entry, built once and checked on the oracle alone for the tables to bite (tests/test_tq.py assert_tables_bite)."""
+    if name not in _table_inputs:
+        from tests.quant_tables import is_asymmetric, mutated, table_size
+        from tests.test_tq import assert_tables_bite
+        kw = dict(TABLE_CASES[name])
+        inp = build_inputs(pkg, **kw)
+        for q in inp["quants"]:
+            assert all(is_asymmetric(q[t], table_size(q)) for t in ("levelscale", "invlevelscale", "leveloffset"))
+        me = oracle_search(inp)
+        modes = inp["modes"] if inp["modes"] is not None else oracle.pick_modes(me["cost"])
+        want = expectation(pkg, inp, me["mv"], modes)
+
+        def differ(ks, how):
+            other = expectation(pkg, dict(inp, quants=mutated(inp["quants"], ks, how)), me["mv"], modes)
+            return download_differences(other, other["recon"], want, inp["t8"], kw["ar"])
+        # the DC set: dct_chroma's 4:2:2 DC path reads its offset and inverse scale at (0, 0) and nothing else (block.c:1263)
+        groups = {"luma4x4": ([0], False), "chroma": ([1], False), "chroma_dc": ([2], True)}
+        if inp["t8"].any():
+            groups["luma8x8"] = ([3], False)
+        assert_tables_bite(differ, groups, name)
+        _table_inputs[name] = inp
+    return _table_inputs[name]
+
+
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_tables_are_asymmetric_where_it_matters(pkg, name):
+    """No GPU: on the oracle, each record of every TABLE_CASES entry changes a compared output when its levelscale, invlevelscale or leveloffset
+    is transposed or its leveloffset flattened to the mean; the qp + 3 DC record, read at (0, 0) alone, when its offset is."""
+    table_inputs(pkg, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_fused_422_frame_stage_asymmetric_tables(pkg, monkeypatch, name):
+    """The fused 4:2:2 stage and the separate kernels on asymmetric scaling matrices and rounding offsets: everything test_fused_422_frame_stage
+    checks -- fused against separate, both against the oracle, records, side records, prediction picture."""
+    inp = table_inputs(pkg, name)                           # asserts that the tables bite before anything is compared
+    run_and_check(pkg, monkeypatch, TABLE_CASES[name], inp)
 
 
 def full_size_inputs(pkg, W, H, qp=28):

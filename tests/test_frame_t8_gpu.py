@@ -7,65 +7,79 @@ import pytest
 from tests import oracle
 from tests.test_frame import synth
 from tests.test_me import lambda_factors, make_mbs
+from tests.quant_tables import scaled_quant
 from tests.test_tq import compare_lists
 
 LUMA_FIELDS = ("levels", "runs", "levels8", "runs8", "coeff_cost", "nonzero", "recon", "fadjust")
 
 
-def scaled_q8(pkg, qp, rng, **kw):
-    """An 8x8 luma quantiser with a non-flat scaling matrix: LevelScale8x8 = (quant_coef8 << 4) / M, InvLevelScale8x8 = dequant_coef8 * M
-    (q_matrix.c CalculateQuant8Param), M drawn from 6..40; the flat tables (M = 16) give quant_coef8 and dequant_coef8 << 4."""
-    q = pkg.flat_quant(qp, 342, is8x8=True, transform8x8_flag=1, **kw)
-    m = rng.integers(6, 41, 64)
-    q["levelscale"] = (q["levelscale"] * 16) // m
-    q["invlevelscale"] = (q["invlevelscale"] // 16) * m
-    return q
+def draw_quants(pkg, rng, qp, kw, scaling, qpc=None):
+    """The frame stage's records: luma 4x4, chroma, chroma DC (qp + 3), luma 8x8. scaling True: the 8x8 record alone carries a scaling
+    matrix; "all": each of the four gets a scaling matrix and per-position rounding offsets of its own (tests/quant_tables.py)."""
+    flat = lambda d: pkg.flat_quant(qp + d, 342, **kw)
+    if scaling == "all":
+        qpc = qp if qpc is None else qpc                     # the chroma quantiser may sit below the luma one (chroma_qp_index_offset)
+        quants = [scaled_quant(pkg, q, rng, False, **kw) for q in (qp, qpc, qpc + 3)] + [scaled_quant(pkg, qp, rng, True, transform8x8_flag=1, **kw)]
+    elif scaling:
+        quants = [flat(0), flat(0), flat(3), scaled_quant(pkg, qp, rng, True, offsets=False, transform8x8_flag=1, **kw)]
+    else:
+        quants = [flat(0), flat(0), flat(3), pkg.flat_quant(qp, 342, is8x8=True, transform8x8_flag=1, **kw)]
+    return np.array(quants, dtype=pkg.QUANT_DTYPE)
 
 
-def run_case(pkg, monkeypatch, *, w, h, qp, cavlc, ar, far, chroma_planes, weighted, scaling, fused, seed, all_t8=False):
+def draw_inputs(pkg, *, w, h, qp, cavlc, ar, far, weighted, scaling, seed, all_t8=False, no_t8=False, qpc=None, **unused):
+    """Everything a case feeds the frame stage with, drawn on the host (no device involved)."""
+    rng = np.random.default_rng(seed)
+    cur, ref = synth(rng, w, h, 1)
+    mbs = make_mbs(pkg, rng, w // 16, h // 16, 4 * far)
+    n = len(mbs)
+    kw = dict(adaptive_rounding=ar, adapt_rnd_weight=4 if ar else 0, cavlc=cavlc)
+    quants = draw_quants(pkg, rng, qp, kw, scaling, qpc)
+    modes = np.zeros(n, dtype=pkg.MB_MODE_DTYPE)
+    modes["mode"] = rng.choice([1, 2, 3, 8], n)
+    modes["b8mode"] = rng.integers(4, 8, (n, 4))
+    t8 = np.ones(n, bool) if all_t8 else rng.integers(0, 2, n).astype(bool)
+    t8[0] = True
+    if no_t8:                                                # a 4x4-only picture: the stage's 4x4 instantiation, three records
+        t8[:] = False
+        quants = quants[:3]
+    modes["b8mode"][t8] = 4
+    modes["pad"][:, 0] = t8
+    wp = None
+    if weighted:
+        wp = {"luma_round": 16, "luma_denom": 5, "chroma_round": 4, "chroma_denom": 3, "weight": np.zeros((16, 3), int), "offset": np.zeros((16, 3), int)}
+        wp["weight"][0], wp["offset"][0] = (29, 9, 7), (4, -2, 1)
+    return dict(cur=cur, ref=ref, mbs=mbs, quants=quants, modes=modes, t8=t8, wp=wp)
+
+
+def run_case(pkg, monkeypatch, *, fused, **case):
     """One frame stage on a fresh context; returns its inputs and everything it left behind."""
     if not fused:
         monkeypatch.setenv("JMHIP_FRAME_FUSED", "0")
     else:
         monkeypatch.delenv("JMHIP_FRAME_FUSED", raising=False)
-    rng = np.random.default_rng(seed)
-    R = 8
-    cur, ref = synth(rng, w, h, 1)
+    w, h, qp, R = case["w"], case["h"], case["qp"], 8
+    out = draw_inputs(pkg, **case)
+    n = len(out["mbs"])
     ctx = pkg.Context(w, h, yuv_format=1, max_refs=1, search_range=R)
     try:
-        ctx.ref_upload(0, *ref)
+        ctx.ref_upload(0, *out["ref"])
         ctx.interp_luma(0)
-        if chroma_planes:
+        if case["chroma_planes"]:
             ctx.interp_chroma(0)
-        ctx.cur_upload(*cur)
-        mbs = make_mbs(pkg, rng, w // 16, h // 16, 4 * far)
-        n = len(mbs)
+        ctx.cur_upload(*out["cur"])
         lam = lambda_factors(qp)
         prm = pkg.MeParams()
         prm.search_mode, prm.search_range, prm.rdopt = -1, R, 1
         prm.level_mv_min, prm.level_mv_max = -511, 511
         prm.lambda_[0], prm.lambda_[1], prm.lambda_[2] = lam
         prm.transform8x8_mode, prm.subpel, prm.partition_mask = 1, 1, (1 << 41) - 1
-        me = ctx.me_frame(prm, mbs)
-        kw = dict(adaptive_rounding=ar, adapt_rnd_weight=4 if ar else 0, cavlc=cavlc)
-        q8 = scaled_q8(pkg, qp, rng, **kw) if scaling else pkg.flat_quant(qp, 342, is8x8=True, transform8x8_flag=1, **kw)
-        quants = np.array([pkg.flat_quant(qp, 342, **kw), pkg.flat_quant(qp, 342, **kw), pkg.flat_quant(qp + 3, 342, **kw), q8], dtype=pkg.QUANT_DTYPE)
-        modes = np.zeros(n, dtype=pkg.MB_MODE_DTYPE)
-        modes["mode"] = rng.choice([1, 2, 3, 8], n)
-        modes["b8mode"] = rng.integers(4, 8, (n, 4))
-        t8 = np.ones(n, bool) if all_t8 else rng.integers(0, 2, n).astype(bool)
-        t8[0] = True
-        modes["b8mode"][t8] = 4
-        modes["pad"][:, 0] = t8
-        wp = None
-        if weighted:
-            wp = {"luma_round": 16, "luma_denom": 5, "chroma_round": 4, "chroma_denom": 3, "weight": np.zeros((16, 3), int), "offset": np.zeros((16, 3), int)}
-            wp["weight"][0], wp["offset"][0] = (29, 9, 7), (4, -2, 1)
-        ctx.frame_wp_set(wp)
+        out["me"] = ctx.me_frame(prm, out["mbs"])
+        ctx.frame_wp_set(out["wp"])
         if fused:
             ctx.frame_keep_prediction()
-        ctx.residual_frame(quants, modes)
-        out = {"got": ctx.residual_download(n), "recon": ctx.recon_download()}
+        ctx.residual_frame(out["quants"], out["modes"])
+        out.update(got=ctx.residual_download(n), recon=ctx.recon_download())
         if fused:
             out["records"], out["records8"], out["pred"] = ctx.residual_records(n), ctx.residual_records8(n), ctx.pred_download()
         else:
@@ -75,7 +89,6 @@ def run_case(pkg, monkeypatch, *, w, h, qp, cavlc, ar, far, chroma_planes, weigh
         out["deblocked"] = ctx.recon_download()
     finally:
         ctx.close()
-    out.update(cur=cur, ref=ref, mbs=mbs, me=me, quants=quants, modes=modes, t8=t8, wp=wp)
     return out
 
 
@@ -176,6 +189,108 @@ def test_fused_t8_frame_stage(pkg, monkeypatch, name):
     check_against_oracle(pkg, a, kw["ar"])
     # the thresholds and the 8x8 lists are exercised somewhere across the parametrisation
     assert (a["got"]["cbp"][a["t8"]] & 15).max() > 0 or kw["qp"] >= 34
+
+
+# Scaling matrices AND per-position rounding offsets, asymmetric, a set of their own for each of luma 4x4, chroma, chroma DC and luma 8x8
+# (the stage takes one chroma quantiser per call, so Cb and Cr share theirs). no_t8: a 4x4-only picture, the stage's 4x4 instantiation.
+# qpc: synth's chroma carries a quarter of the luma's amplitude; at the luma QP its AC levels are too few for the chroma tables to show.
+TABLE_CASES = {
+    "tables_t8_cabac_ar": dict(w=64, h=48, qp=24, cavlc=0, ar=1, far=6, chroma_planes=True, weighted=False, scaling="all", qpc=10, seed=311),
+    "tables_t8_cavlc": dict(w=64, h=48, qp=20, cavlc=1, ar=0, far=6, chroma_planes=False, weighted=False, scaling="all", qpc=10, seed=312),
+    "tables_4x4_only_cavlc_ar": dict(w=64, h=48, qp=26, cavlc=1, ar=1, far=6, chroma_planes=True, weighted=False, scaling="all", qpc=10, no_t8=True, seed=313),
+    "tables_4x4_only_cabac": dict(w=64, h=48, qp=18, cavlc=0, ar=0, far=6, chroma_planes=False, weighted=True, scaling="all", qpc=10, no_t8=True, seed=314),
+    "tables_tail_wave": dict(w=80, h=48, qp=22, cavlc=1, ar=1, far=6, chroma_planes=True, weighted=False, scaling="all", qpc=10, seed=315),   # 15 macroblocks
+}
+
+
+def frame_differences(got, recon, want, t8, ar):
+    """What check_against_oracle compares of the downloads, as the list of names that differ; got / recon: the device's, or a second oracle run's
+    (its "luma" / "chroma" dicts and "recon" pictures)."""
+    bad = []
+
+    def lists(name, *a):
+        try:
+            compare_lists(*a, name)
+        except AssertionError:
+            bad.append(name)
+    gl, wl, gc, wc = got["luma"], want["luma"], got["chroma"], want["chroma"]
+    lists("luma levels", gl["levels"], gl["runs"], wl["levels"], wl["runs"])
+    lists("luma levels8", gl["levels8"][t8], gl["runs8"][t8], wl["levels8"][t8], wl["runs8"][t8])
+    lists("chroma levels", gc["levels"][:, :4, :16], gc["runs"][:, :4, :16], wc["levels"][:, :4, :16], wc["runs"][:, :4, :16])
+    lists("chroma dc_levels", gc["dc_levels"][:, None], gc["dc_runs"][:, None], wc["dc_levels"][:, None], wc["dc_runs"][:, None])
+    same = lambda name, a, b: None if np.array_equal(a, b) else bad.append(name)
+    same("luma coeff_cost", gl["coeff_cost"][~t8], wl["coeff_cost"][~t8])
+    same("luma coeff_cost", gl["coeff_cost"][t8][:, :4], wl["coeff_cost"][t8][:, :4])
+    same("luma recon", gl["recon"], wl["recon"])
+    same("chroma recon", gc["recon"][:, :8, :8], wc["recon"][:, :8, :8])
+    same("chroma ret", gc["ret"], wc["ret"])
+    if ar:
+        same("luma fadjust", gl["fadjust"], wl["fadjust"])
+        same("chroma fadjust", gc["fadjust"][:, :8, :8], wc["fadjust"][:, :8, :8])
+    same("cbp", got["cbp"], want["cbp"])
+    same("cbp_blk", got["cbp_blk"], want["cbp_blk"])
+    for g, wv, name in zip(recon, want["recon"], "YUV"):
+        same("picture recon %s" % name, g, wv)
+    return bad
+
+
+_table_refs = {}
+
+
+def table_reference(pkg, name):
+    """Inputs, the oracle's motion search and its expectation for a TABLE_CASES entry -- built once, checked for the tables to bite, shared."""
+    if name not in _table_refs:
+        from tests.quant_tables import is_asymmetric, mutated, table_size
+        from tests.test_tq import assert_tables_bite
+        kw = TABLE_CASES[name]
+        inp = draw_inputs(pkg, **kw)
+        for q in inp["quants"]:
+            assert all(is_asymmetric(q[t], table_size(q)) for t in ("levelscale", "invlevelscale", "leveloffset"))
+        rp = oracle.RefPic(*inp["ref"], yuv_format=1)
+        me = oracle.me_frame(oracle.me_params(rdopt=1, transform8x8_mode=1), [rp], inp["cur"][0], inp["mbs"], -1, 8, lambda_factors(kw["qp"]))
+        n = len(inp["mbs"])
+        run = lambda quants: oracle.residual_frame([rp], inp["cur"], inp["mbs"], me["mv"], inp["modes"], quants, pkg.TQ_JOB_DTYPE, yuv_format=1,
+                                                   blk_ref=np.zeros((n, 4), int), wp=inp["wp"])
+        want = run(inp["quants"])
+        # 4:2:0 reads its chroma DC from the chroma record at (0, 0) and never opens record 2 (block.c:1094-1107), so no mutation of it can show
+        groups = {"luma4x4": ([0], False), "chroma": ([1], False)}
+        if inp["t8"].any():
+            groups["luma8x8"] = ([3], False)
+        if inp["t8"].all():
+            del groups["luma4x4"]
+
+        def differ(ks, how):
+            other = run(mutated(inp["quants"], ks, how))
+            return frame_differences(other, other["recon"], want, inp["t8"], kw["ar"])
+        assert_tables_bite(differ, groups, name)
+        _table_refs[name] = (inp, me, want)
+    return _table_refs[name]
+
+
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_tables_are_asymmetric_where_it_matters(pkg, name):
+    """No GPU: on the oracle, each of the luma 4x4, chroma and luma 8x8 records of every TABLE_CASES entry changes a compared output when its
+    levelscale, invlevelscale or leveloffset is transposed or its leveloffset flattened to the mean (tests/test_tq.py assert_tables_bite)."""
+    inp, me, want = table_reference(pkg, name)
+    assert TABLE_CASES[name].get("no_t8") or (inp["t8"].any() and (~inp["t8"]).any())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_frame_stage_asymmetric_tables(pkg, monkeypatch, name):
+    """The fused 4:2:0 stage (4x4-only and mixed with 8x8-transform macroblocks) and the separate kernels on asymmetric scaling matrices and
+    rounding offsets: against each other and against the oracle -- result structs, cbp, cbp_blk, reconstruction, dense records, side records,
+    prediction picture."""
+    kw = TABLE_CASES[name]
+    inp, me, want = table_reference(pkg, name)              # asserts that the tables bite before anything is compared
+    a = run_case(pkg, monkeypatch, fused=True, **kw)
+    b = run_case(pkg, monkeypatch, fused=False, **kw)
+    for o in (a, b):
+        assert np.array_equal(o["me"]["mv"], me["mv"]) and o["quants"].tobytes() == inp["quants"].tobytes()
+        assert frame_differences(o["got"], o["recon"], want, inp["t8"], kw["ar"]) == []
+    check_against_separate(a, b)
+    check_against_oracle(pkg, a, kw["ar"])
+    check_against_oracle(pkg, b, kw["ar"], check_records=False)
 
 
 @pytest.mark.gpu

@@ -304,3 +304,63 @@ def test_dct_chroma_matches_jm(path):
             mask = np.ones((rows, cols), bool)
             mask[::4, ::4] = False
             assert np.array_equal(gfa[:rows, :cols][mask], fadj[mask])
+
+
+ASYM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "high_t8_qmatrix_qoffset_asym.npz")
+
+
+def test_asymmetric_tables_fixture():
+    """high_t8_qmatrix_qoffset_asym.npz was captured with a QmatrixFile and a QOffsetMatrixFile whose lists change under a swap of row and column:
+    every dct record carries LevelScale, InvLevelScale and LevelOffset tables with T != T.T, for intra and inter blocks, 4x4 and 8x8. The
+    test_dct_*_matches_jm cases above replay them, so the oracle's [j][i] is JM's. That the records can tell: with any one table transposed
+    the oracle's dct_4x4 / dct_8x8 stops matching JM on some record."""
+    z = np.load(ASYM)
+    L = oracle.lib()
+    vp = C.c_void_p
+    L.jmo_dct_4x4.argtypes = [C.POINTER(oracle.Quant), vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int), vp, vp, vp, vp]
+    L.jmo_dct_8x8.argtypes = [C.POINTER(oracle.Quant), vp, vp, C.c_int, C.POINTER(C.c_int), vp, vp, vp, vp]
+    tables = ("levelscale", "invlevelscale", "leveloffset")
+    for kind, skip, n in (("dct4", 4, 4), ("dct8", 3, 8), ("dct16", 1, 4), ("dctc", 5, 4)):
+        rs = recs(z, kind)
+        assert len(rs) >= 20, kind
+        for r in rs:
+            q, a = quant_from(r[skip:], n)
+            for t in tables + (() if kind != "dctc" else ()):
+                T = q[t][:n * n].reshape(n, n)
+                assert not np.array_equal(T, T.T), (kind, t)
+            if kind == "dctc":                         # the DC record (read at (0, 0) alone) is a full asymmetric table as well
+                qdc, _ = quant_from(a, 4)
+                assert not np.array_equal(qdc["leveloffset"][:16].reshape(4, 4), qdc["leveloffset"][:16].reshape(4, 4).T)
+    assert {int(r[2]) for r in recs(z, "dct4")} == {0, 1} and {int(r[1]) for r in recs(z, "dct8")} == {0, 1}, "intra and inter records"
+
+    def mismatches(kind, t):
+        bad = 0
+        for r in recs(z, kind):
+            n = 4 if kind == "dct4" else 8
+            q, a = quant_from(r[4 if kind == "dct4" else 3:], n)
+            if t:
+                q[t][:n * n] = q[t][:n * n].reshape(n, n).T.reshape(-1)
+            m7 = np.ascontiguousarray(a[:256].reshape(16, 16), np.int32)
+            mpr = np.ascontiguousarray(a[256:512].reshape(16, 16), np.uint16)
+            o = a[512:]
+            qh = oracle.QuantHolder(q)
+            grec, gfa = np.zeros((16, 16), np.uint16), np.zeros((16, 16), np.int32)
+            if kind == "dct4":
+                bx, by, cost = int(r[0]), int(r[1]), C.c_int(int(r[3]))
+                gl, gr = np.zeros(17, np.int32), np.zeros(17, np.int32)
+                got = L.jmo_dct_4x4(C.byref(qh.c), m7.ctypes.data, mpr.ctypes.data, bx, by, C.byref(cost), gl.ctypes.data, gr.ctypes.data, grec.ctypes.data, gfa.ctypes.data)
+                ok = (got, cost.value) == (int(o[0]), int(o[1])) and lists_equal(gl, gr, o[2:19], o[19:36]) and np.array_equal(grec[by:by + 4, bx:bx + 4], o[36:52].reshape(4, 4))
+            else:
+                b8, cost = int(r[0]), C.c_int(int(r[2]))
+                gl, gr = np.zeros((4, 65), np.int32), np.zeros((4, 65), np.int32)
+                got = L.jmo_dct_8x8(C.byref(qh.c), m7.ctypes.data, mpr.ctypes.data, b8, C.byref(cost), gl.ctypes.data, gr.ctypes.data, grec.ctypes.data, gfa.ctypes.data)
+                lr = o[2:2 + 4 * 130].reshape(4, 2, 65)
+                ys, xs = 8 * (b8 >> 1), 8 * (b8 & 1)
+                ok = (got, cost.value) == (int(o[0]), int(o[1])) and all(lists_equal(gl[k], gr[k], lr[k, 0], lr[k, 1]) for k in range(4 if (q["transform8x8_flag"] and q["cavlc"]) else 1)) \
+                    and np.array_equal(grec[ys:ys + 8, xs:xs + 8], o[2 + 520:2 + 520 + 64].reshape(8, 8))
+            bad += not ok
+        return bad
+    for kind in ("dct4", "dct8"):
+        assert mismatches(kind, None) == 0
+        for t in tables:
+            assert mismatches(kind, t) > 0, "%s: a transposed %s still matches JM on every record" % (kind, t)

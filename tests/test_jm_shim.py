@@ -75,15 +75,41 @@ DisableIntraInInter = {noi}
 QM_KEYS = "QmatrixFile = \"qm.cfg\"\nScalingMatrixPresentFlag = 1\n" + "".join("ScalingListPresentFlag%d = 1\n" % i for i in range(8))
 
 
-def write_qmatrix(path):
+def write_qmatrix(path, asym=False, same_chroma=False):
+    """same_chroma: the Cr lists repeat the Cb ones (the frame-stage binding takes one chroma quantiser per call and steps aside otherwise). asym: a term in the row alone, so that no list equals its transpose (M[j][i] != M[i][j] off the diagonal) -- the symmetric lists cannot
+    tell LevelScale[j][i] from LevelScale[i][j] anywhere between JM's tables and the device's records."""
     names4 = ["INTRA4X4_LUMA", "INTRA4X4_CHROMAU", "INTRA4X4_CHROMAV", "INTER4X4_LUMA", "INTER4X4_CHROMAU", "INTER4X4_CHROMAV"]
     with open(path, "w") as f:
         for k, name in enumerate(names4):
-            m = [[min(255, 8 + k + (3 + (k & 1)) * (i + j) + (2 if i == j else 0)) for i in range(4)] for j in range(4)]
+            if same_chroma and name.endswith("CHROMAV"):
+                k -= 1
+            m = [[min(255, 8 + k + (3 + (k & 1)) * (i + j) + (2 if i == j else 0) + ((3 * j - i) if asym else 0)) for i in range(4)] for j in range(4)]
+            assert not asym or m != [list(r) for r in zip(*m)]
             f.write("%s =\n%s\n\n" % (name, ",\n".join(",".join("%d" % v for v in row) for row in m)))
         for k, name in enumerate(["INTRA8X8_LUMA", "INTER8X8_LUMA"]):
-            m = [[min(255, 9 + 3 * k + 2 * (i + j) + (i * j) // 3) for i in range(8)] for j in range(8)]
+            m = [[min(255, 9 + 3 * k + 2 * (i + j) + (i * j) // 3 + ((2 * j - i) if asym else 0)) for i in range(8)] for j in range(8)]
+            assert not asym or m != [list(r) for r in zip(*m)]
             f.write("%s =\n%s\n\n" % (name, ",\n".join(",".join("%d" % v for v in row) for row in m)))
+
+
+# Rounding offsets per position (q_offsets.c:23-58 names the lists): 11-bit values between 1/12 and 5/12 of a quantiser step, this test's own,
+# different for every list and none equal to its transpose. JM shifts them into LevelOffset4x4Comp / LevelOffset8x8Comp [j][i] (q_offsets.c:491-).
+QO_KEYS = "QOffsetMatrixFile = \"qo.cfg\"\nOffsetMatrixPresentFlag = 1\n"
+
+
+def write_qoffsets(path, same_chroma=False):
+    kinds = ["INTRA", "INTERP", "INTERB"]
+    names4 = ["INTRA4X4_%s_%s" % (c, k) for k in kinds for c in ("LUMA", "CHROMAU", "CHROMAV")] + \
+             ["INTER4X4_%s_%s" % (c, k) for k in kinds[1:] for c in ("LUMA", "CHROMAU", "CHROMAV")]
+    names8 = [n % c for c in ("LUMA", "CHROMAU", "CHROMAV") for n in ("INTRA8X8_%s_INTRA", "INTRA8X8_%s_INTERP", "INTRA8X8_%s_INTERB", "INTER8X8_%s_INTERP", "INTER8X8_%s_INTERB")]
+    with open(path, "w") as f:
+        for n, names in ((4, names4), (8, names8)):
+            for k, name in enumerate(names):
+                if same_chroma and "CHROMAV" in name:
+                    k = names.index(name.replace("CHROMAV", "CHROMAU"))
+                m = [[171 + (37 * k + 97 * j + 29 * i + 11 * i * j * j) % 683 for i in range(n)] for j in range(n)]
+                assert m != [list(r) for r in zip(*m)]
+                f.write("%s =\n%s\n\n" % (name, ",\n".join(",".join("%d" % v for v in row) for row in m)))
 
 CASES = {
     # name: cfg values                                                                      what it exercises
@@ -125,6 +151,10 @@ CASES = {
     # scaling matrices (q_matrix.c:451-738): non-flat LevelScale / InvLevelScale tables for every 4x4 list and the 8x8 luma lists, I / P / B, adaptive rounding on
     "fastfull_high_qmatrix": dict(search=0, profile=100, cabac=1, t8x8=1, bframes=1, refs=2, rdopt=1, adrnd=1, yuv=1, qmatrix=1),
     "full_high_qmatrix_cavlc_lowcplx": dict(search=-1, profile=100, cabac=0, t8x8=1, bframes=0, refs=1, rdopt=0, adrnd=0, yuv=1, qmatrix=1, qp=34),
+    # the same with lists that change under a swap of row and column, and rounding offsets per position (QOffsetMatrixFile) that do so too: what
+    # tells [j][i] from [i][j] in the binding's table copies (fill_quant and the slice parameters' t8 tables) and in every kernel behind them
+    "fastfull_high_qmatrix_asym": dict(search=0, profile=100, cabac=1, t8x8=1, bframes=0, refs=1, rdopt=1, adrnd=0, yuv=1, qmatrix=2),
+    "full_high_qmatrix_asym_cavlc_lowcplx": dict(search=-1, profile=100, cabac=0, t8x8=1, bframes=0, refs=1, rdopt=0, adrnd=0, yuv=1, qmatrix=2, qp=30),
 }
 
 
@@ -173,9 +203,12 @@ def prepare(tmp_path, name, w=176, h=144, frames=3, R=16, qp=28):
     v.setdefault("wbp", 0)
     v.setdefault("wp", 0)
     v.setdefault("noi", 0)
-    v["extra"] = QM_KEYS if v.get("qmatrix") else ""
+    # qmatrix 1: symmetric lists; 2: asymmetric lists and per-position offsets; 3: the same with Cr repeating Cb
+    v["extra"] = (QM_KEYS if v.get("qmatrix") else "") + (QO_KEYS if v.get("qmatrix", 0) >= 2 else "")
     if v.get("qmatrix"):
-        write_qmatrix(tmp_path / "qm.cfg")
+        write_qmatrix(tmp_path / "qm.cfg", asym=v["qmatrix"] >= 2, same_chroma=v["qmatrix"] == 3)
+    if v.get("qmatrix", 0) >= 2:
+        write_qoffsets(tmp_path / "qo.cfg", same_chroma=v["qmatrix"] == 3)
     with open(tmp_path / "case.cfg", "w") as f:
         f.write(CFG.format(**v))
     make_clip(tmp_path / "clip.yuv", w, h, frames + v["bframes"] * (frames - 1), v["yuv"], v.get("fade", 0), v.get("diverse", 0))
@@ -264,6 +297,11 @@ SLICE_CASES = {
     "slice_umhex_sse_hpel": dict(search=1, profile=66, cabac=0, t8x8=0, bframes=0, refs=2, rdopt=0, adrnd=1, yuv=1, noi=1, fpel=0, hpel=1, qpel=2),
     "slice_full_sse_subpel_t8": dict(search=-1, profile=100, cabac=1, t8x8=1, bframes=0, refs=1, rdopt=0, adrnd=0, yuv=1, noi=1, fpel=0, hpel=1, qpel=1, mdm=1, qp=32),
     "slice_full_range40": dict(search=-1, profile=66, cabac=0, t8x8=0, bframes=0, refs=2, rdopt=0, adrnd=1, yuv=1, noi=1, R=40),      # the widest range of the sweeps over the frame kernels
+    # asymmetric scaling lists and per-position rounding offsets in the slice binding, Cr repeating Cb so that the frame stage stays bound: the
+    # 4x4 frame stage answers every dct_4x4 / dct_chroma from records quantised with fill_quant's copies (asserted below: it ran), and with
+    # Transform8x8Mode 1 the slice parameters' copy of the 8x8 tables (t8_levelscale / t8_leveloffset) feeds the search's transform decision
+    "slice_fastfull_qmatrix_asym": dict(search=0, profile=100, cabac=0, t8x8=0, bframes=0, refs=2, rdopt=0, adrnd=0, yuv=1, noi=1, qmatrix=3),
+    "slice_fastfull_t8_qmatrix_asym": dict(search=0, profile=100, cabac=1, t8x8=1, bframes=0, refs=2, rdopt=0, adrnd=0, yuv=1, noi=1, qmatrix=3, qp=36),
     "slice_umhex_5ref_t8": dict(search=1, profile=100, cabac=1, t8x8=1, bframes=0, refs=5, rdopt=0, adrnd=0, yuv=1, noi=1, frames=7, qp=32),
 }
 CASES.update(SLICE_CASES)

@@ -96,7 +96,7 @@ def synth_clip(rng, W, H, nframes):
     return load_pkg().slice_host.synth_clip(rng, W, H, nframes)
 
 
-def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=(0, 2, 2), qp=28, max_mbs=None, t8=0, cavlc=1, wp=None, one_call=False, rdopt=0, map_log=None, map_init=None, what_if=None, ideal_map=False, first_touch=None, md_metric=2):
+def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=(0, 2, 2), qp=28, max_mbs=None, t8=0, cavlc=1, wp=None, one_call=False, rdopt=0, map_log=None, map_init=None, what_if=None, ideal_map=False, first_touch=None, md_metric=2, q8=None):
     """Frames 1.. are coded as P pictures against the previous `nref` SOURCE frames (the search does not care where a reference came from)."""
     rng = np.random.default_rng(seed)
     clip = synth_clip(rng, W, H, nframes + nref - 1)
@@ -136,7 +136,7 @@ def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=
         for s in range(slices):
             first, count = s * per, min(per, nmb - s * per)
             q = oracle.lowcplx_params(mode, R, nref, lam3, ref_cost1, W, H, epzs=epzs, umhex=umhex, all_mv_state=all_mv_state, metric=metric,
-                                      transform8x8_mode=t8, qp=qp, cavlc=cavlc, rdopt=rdopt, md_metric=md_metric)
+                                      transform8x8_mode=t8, qp=qp, cavlc=cavlc, rdopt=rdopt, md_metric=md_metric, q8=q8)
             if wp:                                       # explicit weighted prediction, used in the search too (UseWeightedReferenceME): (denominator, [(weight, offset)] per reference)
                 q.wp_pred, q.me.apply_weights = 1, 1
                 q.me.luma_log_weight_denom, q.me.wp_luma_round = wp[0], (1 << (wp[0] - 1)) if wp[0] else 0
@@ -152,7 +152,7 @@ def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=
             if one_call:                                 # the device searches all slices of the picture in ONE call (slice_mbs) below
                 wants.append(want)
                 continue
-            p = slice_params(pkg, mode, R, nref, lam3, ref_cost1, W, mb_first=first, mb_count=count, metric=metric, qp_n=qp, t8=t8, cavlc=cavlc, rdopt=rdopt, md_metric=md_metric)
+            p = slice_params(pkg, mode, R, nref, lam3, ref_cost1, W, mb_first=first, mb_count=count, metric=metric, qp_n=qp, t8=t8, cavlc=cavlc, rdopt=rdopt, md_metric=md_metric, q8=q8)
             if mode == 3:
                 lib.jmhip_epzs_scales(p, 2 * f, (C.c_int * nref)(*pocs), nref)
             if wp:
@@ -165,7 +165,7 @@ def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=
             if map_log is not None:                      # EPZS: (aliased map tests of this slice, searches so far) on the device and in the oracle
                 map_log.append((ctx.epzs_map_info(), (epzs.alias_events() - sum(m[1][0] for m in map_log), epzs.search_count())))
         if one_call:
-            p = slice_params(pkg, mode, R, nref, lam3, ref_cost1, W, mb_first=0, mb_count=nmb, metric=metric, qp_n=qp, t8=t8, cavlc=cavlc, rdopt=rdopt, md_metric=md_metric)
+            p = slice_params(pkg, mode, R, nref, lam3, ref_cost1, W, mb_first=0, mb_count=nmb, metric=metric, qp_n=qp, t8=t8, cavlc=cavlc, rdopt=rdopt, md_metric=md_metric, q8=q8)
             p.slice_mbs = per
             if mode == 3:
                 lib.jmhip_epzs_scales(p, 2 * f, (C.c_int * nref)(*pocs), nref)
@@ -499,3 +499,97 @@ def test_call_records_for_the_high_complexity_modes(pkg, mode, slices, t8):
     """rdopt != 0: BlockMotionSearch without what JM does only with RDOptimization off (centre clamp, zero-vector bonuses, pos_00 pre-check, skip
     shortcut) -- the records the JM binding answers from, speculatively, when the encoder runs its rate-distortion decision."""
     run_synthetic(pkg, mode, 176, 144, 16, 2, slices=slices, rdopt=1, t8=t8, qp=30, one_call=slices > 1)
+
+
+# ------------------------------------------------------------------ the transform decision on a position-dependent, asymmetric 8x8 quantiser
+
+T8_TABLE_W, T8_TABLE_H, T8_TABLE_R, T8_TABLE_NREF = 96, 64, 8, 2           # the smallest clip of test_transform8x8_modes_match_the_oracle
+
+
+def oracle_slices(mode, q8, qp, seed=5, nframes=3):
+    """run_synthetic's oracle half alone (no device): the records of every P picture of the clip, one slice each, Transform8x8Mode 1 with q8."""
+    W, H, R, nref = T8_TABLE_W, T8_TABLE_H, T8_TABLE_R, T8_TABLE_NREF
+    rng = np.random.default_rng(seed)
+    clip = synth_clip(rng, W, H, nframes + nref - 1)
+    lam = int(65536 * np.sqrt(0.85 * 2 ** ((qp - 12) / 3.0)) + 0.5)
+    ref_cost1 = int(2 * np.sqrt(0.85 * 2 ** ((qp - 12) / 3.0)))
+    epzs = oracle.Epzs(W, H, R, nref) if mode == 3 else None
+    umhex = oracle.Umhex(W, H, R, nref, qp) if mode == 1 else None
+    all_mv_state = np.zeros((4, 4, oracle.MAX_REFS, 9, 2), np.int16)
+    prev_field = [(np.zeros((H // 4, W // 4, 2), np.int16), np.full((H // 4, W // 4), -1, np.int64))] * 2
+    out = []
+    for f in range(nref, nref + nframes - 1):
+        pocs = [2 * (f - 1 - r) for r in range(nref)]
+        orefs = [oracle.RefPic(clip[f - 1 - r], yuv_format=0) for r in range(nref)]
+        if epzs:
+            epzs.slice_init(2 * f, pocs, pocs, [prev_field[0][0], prev_field[1][0]], [prev_field[0][1], prev_field[1][1]])
+        ref_idx = np.full((H // 4, W // 4), -1, np.int8)
+        mvf = np.zeros((H // 4, W // 4, 2), np.int16)
+        q = oracle.lowcplx_params(mode, R, nref, [lam] * 3, ref_cost1, W, H, epzs=epzs, umhex=umhex, all_mv_state=all_mv_state,
+                                  transform8x8_mode=1, qp=qp, cavlc=1, q8=q8)
+        sid = np.zeros((W // 16) * (H // 16), np.int32)
+        q._sid = sid
+        q.slice_id = sid.ctypes.data
+        out.append(oracle.lowcplx_p_slice(q, orefs, clip[f], ref_idx, mvf)[0])
+        ids = np.where(ref_idx >= 0, np.array(pocs, np.int64)[np.clip(ref_idx, 0, None)], -1)
+        prev_field = [(mvf.copy(), ids), prev_field[0]]
+    for o in (epzs, umhex):
+        if o:
+            o.close()
+    return np.concatenate(out)
+
+
+# The quantiser enters the decision in one place: a P8x8 macroblock whose 8x8-transform pass won keeps it only if dct_8x8 leaves a coded block
+# (coefficient cost > 4, md_low.c:547). That is a handful of macroblocks of a 48-macroblock picture, and a swap of row and column moves a cost
+# across 4 only under a coarse quantiser: (qp, clip seed) per search mode below were found on the oracle alone (the table seed is 53 for all).
+# Third entry: each of levelscale^T and leveloffset^T ALONE moves a decision. For EPZS no such input was found among 4 qp x 79 clip seeds;
+# there only the two transposed together are shown to bite, so a kernel that mis-indexes one of the two tables alone could pass mode 3.
+T8_TABLE_CASES = {-1: (38, 10, True), 0: (38, 10, True), 1: (38, 10, True), 3: (44, 36, False)}
+
+
+def t8_table_case(pkg, mode):
+    from tests.quant_tables import scaled_quant
+    qp, clip_seed = T8_TABLE_CASES[mode][:2]
+    return qp, clip_seed, scaled_quant(pkg, qp, np.random.default_rng(53), True, transform8x8_flag=1, cavlc=1)
+
+
+T8_DECISION = ("transform8x8_flag", "best_mode", "b8mode", "cbp8ts")
+
+
+def assert_t8_tables_bite(pkg, mode):
+    """On the oracle: the decision takes the 8x8 transform for some macroblocks and the 4x4 one for others, and the transposed table -- levelscale
+    and leveloffset read at [i][j], which is what the slice parameters carry of the quantiser -- changes it for at least one macroblock; where
+    T8_TABLE_CASES says so, each of the two transposed alone does as well."""
+    from tests.quant_tables import is_asymmetric, mutated
+    qp, clip_seed, q8 = t8_table_case(pkg, mode)
+    assert is_asymmetric(q8["levelscale"], 8) and is_asymmetric(q8["leveloffset"], 8)
+    want = oracle_slices(mode, q8, qp, seed=clip_seed)
+    flag = want["transform8x8_flag"]
+    assert (flag == 1).any() and (flag == 0).any()
+    one = lambda how, q: mutated(np.array([q], dtype=pkg.QUANT_DTYPE), [0], how)[0]
+    variants = {"levelscale^T and leveloffset^T": one("leveloffset^T", one("levelscale^T", q8))}
+    if T8_TABLE_CASES[mode][2]:
+        variants.update({how: one(how, q8) for how in ("levelscale^T", "leveloffset^T")})
+    for how, swapped in variants.items():
+        other = oracle_slices(mode, swapped, qp, seed=clip_seed)
+        changed = np.zeros(len(want), bool)
+        for f in T8_DECISION:
+            changed |= (other[f] != want[f]).reshape(len(want), -1).any(axis=1)
+        assert changed.any(), "SearchMode %d: %s changes no macroblock's decision" % (mode, how)
+
+
+@pytest.mark.parametrize("mode", [-1, 0, 1, 3])
+def test_tables_are_asymmetric_where_it_matters(pkg, mode):
+    """No GPU: the input condition of test_transform_decision_on_asymmetric_tables, on the oracle alone."""
+    assert_t8_tables_bite(pkg, mode)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [-1, 0, 1, 3])
+def test_transform_decision_on_asymmetric_tables(pkg, mode):
+    """Transform8x8Mode 1 with an inter 8x8 luma quantiser whose scaling matrix and rounding offsets depend on (j, i) and are not symmetric:
+    the coded-block pattern of the 8x8-transform P8x8 pass (dct_8x8's quantisation in the search kernel) and with it the decision, per search
+    mode, against the oracle."""
+    assert_t8_tables_bite(pkg, mode)
+    qp, clip_seed, q8 = t8_table_case(pkg, mode)
+    run_synthetic(pkg, mode, T8_TABLE_W, T8_TABLE_H, T8_TABLE_R, T8_TABLE_NREF, t8=1, qp=qp, q8=q8, seed=clip_seed)

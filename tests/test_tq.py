@@ -125,3 +125,147 @@ def test_flat_tables_match_oracle(pkg):
             ls, ils, lo, n = oracle.flat_tables(qp, 342, is8)
             assert np.array_equal(q["levelscale"][:n], ls[:n]) and np.array_equal(q["invlevelscale"][:n], ils[:n])
             assert np.array_equal(q["leveloffset"][:n], lo[:n])
+
+
+# ------------------------------------------------------------------ position-dependent, asymmetric tables (tests/quant_tables.py)
+
+AR = dict(adaptive_rounding=1, adapt_rnd_weight=4)
+TABLE_CASES = {
+    "luma4x4_ar": dict(kind="luma4x4", qps=[4, 17, 28, 36, 45], n=300, amp=12, cavlc=1, **AR),
+    "luma4x4_field": dict(kind="luma4x4", qps=[10, 22, 31], n=200, amp=25, cavlc=0, field_scan=1),
+    "luma8x8_interleaved_ar": dict(kind="luma8x8", qps=[6, 20, 28, 40], n=200, amp=15, cavlc=1, transform8x8_flag=1, **AR),
+    "luma8x8_lists64": dict(kind="luma8x8", qps=[12, 26, 33], n=200, amp=15, cavlc=0, transform8x8_flag=1),
+    "luma8x8_lists64_field_ar": dict(kind="luma8x8", qps=[18, 30], n=200, amp=10, cavlc=0, transform8x8_flag=1, field_scan=1, **AR),
+    "luma16x16_ar": dict(kind="luma16x16", qps=[5, 8, 28, 44], n=200, amp=25, cavlc=1, **AR),
+    "luma16x16": dict(kind="luma16x16", qps=[20, 30], n=200, amp=8, cavlc=0),
+    "chroma420_ar": dict(kind="chroma", fmt=1, qps=[3, 12, 24, 33, 39], n=300, amp=10, cavlc=1, **AR),
+    "chroma420": dict(kind="chroma", fmt=1, qps=[16, 27], n=200, amp=6, cavlc=1),
+    "chroma422_ar": dict(kind="chroma", fmt=2, qps=[3, 12, 24, 33, 39], n=300, amp=10, cavlc=1, **AR),
+    "chroma422": dict(kind="chroma", fmt=2, qps=[9, 21, 30], n=200, amp=6, cavlc=0),
+}
+
+
+def table_case(pkg, name):
+    """quants, jobs, groups of a TABLE_CASES entry, drawn on the host. groups: {name: (record indices, is a DC-only set)}. Chroma: the Cb jobs
+    use records [0, n), the Cr jobs [n, 2n), and their DC quantisers (the qp + 3 sets, read by the 4:2:2 DC path alone) [2n, 3n) and [3n, 4n):
+    four families of tables, no two alike."""
+    from tests.quant_tables import scaled_quant
+    kw = dict(TABLE_CASES[name])
+    kind, qps, n, amp, fmt = kw.pop("kind"), kw.pop("qps"), kw.pop("n"), kw.pop("amp"), kw.pop("fmt", 1)
+    rng = np.random.default_rng(7000 + sorted(TABLE_CASES).index(name))
+    is8 = kind == "luma8x8"
+    nq = len(qps)
+    if kind != "chroma":
+        quants = np.array([scaled_quant(pkg, qp, rng, is8, **kw) for qp in qps], dtype=pkg.QUANT_DTYPE)
+        jobs = make_jobs(pkg, rng, n, nq, amp)
+        return kind, fmt, quants, jobs, {"all": (list(range(nq)), False)}
+    quants = np.array([scaled_quant(pkg, qp + d, rng, False, **kw) for d in (0, 0, 3, 3) for qp in qps], dtype=pkg.QUANT_DTYPE)
+    quants["img_qp"] = qps * 4
+    jobs = make_jobs(pkg, rng, n, nq, amp, chroma=True)
+    jobs["quant"] += nq * jobs["uv"]
+    jobs["quant_dc"] = jobs["quant"] + 2 * nq
+    groups = {"cb": (list(range(nq)), False), "cr": (list(range(nq, 2 * nq)), False)}
+    if fmt == 2:
+        groups["cb_dc"], groups["cr_dc"] = (list(range(2 * nq, 3 * nq)), True), (list(range(3 * nq, 4 * nq)), True)
+    return kind, fmt, quants, jobs, groups
+
+
+def tq_differences(kind, fmt, got, want, adaptive):
+    """The comparisons of test_dct_* as a list of the names that differ (empty: equal); got is the device's result or a second oracle run."""
+    bad = []
+
+    def lists(name, *a):
+        try:
+            compare_lists(*a, name)
+        except AssertionError:
+            bad.append(name)
+
+    def same(name, a, b):
+        if not np.array_equal(a, b):
+            bad.append(name)
+    if kind == "luma4x4":
+        lists("levels", got["levels"], got["runs"], want["levels"], want["runs"])
+        for k in ("recon", "coeff_cost", "nonzero"):
+            same(k, got[k], want[k])
+    elif kind == "luma8x8":
+        lists("levels", got["levels"], got["runs"], want["levels"], want["runs"])
+        lists("levels", got["levels8"], got["runs8"], want["levels8"], want["runs8"])
+        same("recon", got["recon"], want["recon"])
+        for k in ("coeff_cost", "nonzero"):
+            same(k, got[k][:, :4], want[k][:, :4])
+    elif kind == "luma16x16":
+        lists("dc_levels", got["dc_levels"][:, None, :], got["dc_runs"][:, None, :], want["dc_levels"][:, None, :], want["dc_runs"][:, None, :])
+        lists("levels", got["levels"][:, :, :16], got["runs"][:, :, :16], want["levels"][:, :, :16], want["runs"][:, :, :16])
+        for k in ("recon", "ret"):
+            same(k, got[k], want[k])
+    else:
+        nblk = 4 if fmt == 1 else 8
+        rows, cols = (8, 8) if fmt == 1 else (16, 8)
+        lists("dc_levels", got["dc_levels"][:, None, :], got["dc_runs"][:, None, :], want["dc_levels"][:, None, :], want["dc_runs"][:, None, :])
+        lists("levels", got["levels"][:, :nblk, :16], got["runs"][:, :nblk, :16], want["levels"][:, :nblk, :16], want["runs"][:, :nblk, :16])
+        same("recon", got["recon"][:, :rows, :cols], want["recon"][:, :rows, :cols])
+        same("ret", got["ret"], want["ret"])
+        same("cbp_blk", got["cbp_blk"], want["cbp_blk"] & ~want["cbp_clear"])
+        same("cbp_clear", got["cbp_clear"], want["cbp_clear"])
+    if adaptive:
+        rows, cols = (16, 16) if kind != "chroma" else ((8, 8) if fmt == 1 else (16, 8))
+        same("fadjust", got["fadjust"][:, :rows, :cols], want["fadjust"][:, :rows, :cols])
+    return bad
+
+
+def assert_tables_bite(differ, groups, what):
+    """The condition on the inputs that makes a passing comparison mean something: every way of getting a table wrong (quant_tables.MUTATIONS)
+    changes a compared output of the oracle. differ(ks, how) -> names of the compared outputs that change when the records ks are mutated."""
+    from tests.quant_tables import MUTATIONS
+    for gname, (ks, dc_only) in groups.items():
+        for how in MUTATIONS:
+            if dc_only and how != "leveloffset=mean":
+                continue                                    # a DC-only set is read at (0, 0): transposing it is no change at all
+            bad = differ(ks, how)
+            assert bad, "%s: %s of the %s records changes nothing that is compared" % (what, how, gname)
+            if how.startswith("leveloffset"):
+                assert any("levels" in b for b in bad), "%s: %s of %s leaves every level in place (%s)" % (what, how, gname, bad)
+            if how == "invlevelscale^T":
+                assert any("recon" in b for b in bad), "%s: %s of %s leaves the reconstruction in place (%s)" % (what, how, gname, bad)
+
+
+_table_refs = {}
+
+
+def table_reference(pkg, name):
+    """The oracle's result of a TABLE_CASES entry, checked once for the tables to bite and then shared (read-only) by the tests that need it."""
+    if name not in _table_refs:
+        from tests.quant_tables import is_asymmetric, mutated
+        kind, fmt, quants, jobs, groups = table_case(pkg, name)
+        n = 64 if kind == "luma8x8" else 16
+        assert all(is_asymmetric(q[t], 8 if n == 64 else 4) for q in quants for t in ("levelscale", "invlevelscale", "leveloffset"))
+        assert len({q[t][:n].tobytes() for q in quants for t in ("levelscale", "leveloffset")}) == 2 * len(quants), "two records share a table"
+        want = oracle.tq_reference(kind, quants, jobs, yuv_format=fmt)
+        for v in want.values():
+            v.setflags(write=False)
+        ar = int(quants[0]["adaptive_rounding"])
+        if kind == "chroma":                                # as test_dct_chroma compares: the oracle's set bits less its cleared bits
+            straight = dict(want, cbp_blk=want["cbp_blk"] & ~want["cbp_clear"])
+        else:
+            straight = want
+        assert_tables_bite(lambda ks, how: tq_differences(kind, fmt, straight, oracle.tq_reference(kind, mutated(quants, ks, how), jobs, yuv_format=fmt), ar),
+                           groups, name)
+        _table_refs[name] = (kind, fmt, quants, jobs, want, ar)
+    return _table_refs[name]
+
+
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_tables_are_asymmetric_where_it_matters(pkg, name):
+    """No GPU. Every table of every record differs from its transpose and from every other record's, and on the oracle a transposed
+    levelscale, invlevelscale or leveloffset, or a leveloffset flattened to its mean, changes what test_tq_batch_asymmetric_tables compares
+    (offsets: the levels; invlevelscale: the reconstruction), per family of records -- Cb, Cr and, in 4:2:2, their qp + 3 DC sets."""
+    table_reference(pkg, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_tq_batch_asymmetric_tables(pkg, ctx, name):
+    """jmhip_tq_batch on scaling matrices and rounding offsets that depend on (j, i) and are not symmetric: the fields the flat tests compare."""
+    kind, fmt, quants, jobs, want, ar = table_reference(pkg, name)        # asserts that the tables bite before anything is compared
+    got = ctx.tq_batch(kind, quants, jobs, yuv_format=fmt)
+    assert tq_differences(kind, fmt, got, want, ar) == []
