@@ -24,7 +24,8 @@
 // Kernels of this file:
 //   me_int_kernel        generic integer search: any partition mask, any spread of centres (union window in LDS, lane <-> candidate)
 //   me_int_fast_kernel   one lane per candidate column, rolling register window, 2R+1 >= 64 (JMHIP_ME_KERNEL=single)
-//   me_int_pair_kernel   DEFAULT: a candidate's 16x16 block split across a lane pair, 3 waves/SIMD, 2R+1 >= 32
+//   me_int_pair_kernel   DEFAULT: a candidate's 16x16 block split across a lane pair, 3 waves/SIMD, 2R+1 >= 32; two item bodies
+//                        (pair_item<UNI>): one predictor per macroblock -> mv-bit counts in place, otherwise per-partition tables
 // Roofline: ~10^3 integer ops per byte of compulsory traffic -> integer-VALU bound, not HBM bound.
 #include "me_common.h"
 
@@ -693,7 +694,7 @@ constexpr int SLOT_UNUSED = 0x7fffffff;
 struct PairShared {                                   // 2R+1 <= 81 on this path (host check)
   int px[JMHIP_NPART], py[JMHIP_NPART];
   int spx[48], spy[48];                               // predictor of table slot half * 24 + local (SLOT_UNUSED: none)
-  unsigned chg[96];
+  unsigned chg[96];                                   // (spx, spy, chg, bytab, bxtab: the table body only; one-predictor items leave them alone)
   uint8_t bytab[96][48] __attribute__((aligned(16)));    // [row][half * 24 + local]: vertical mv bits
   uint8_t bxtab[84][48] __attribute__((aligned(16)));    // [column][half * 24 + local]: horizontal mv bits
   uint32_t cur[64];
@@ -705,54 +706,38 @@ __device__ __forceinline__ unsigned quad_swap_add(unsigned v)
   return v + (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]: the partner lane
 }
 
-// LIST: the work items are a device-resident list whose LENGTH is device-resident too (*n_items_dev; the slice search's relaxation sweeps,
-// me_xslice.hip, build it on the device and must not wait for the host): a fixed grid strides over it, one item per trip.
-#ifndef JMHIP_PAIR_LIST_WAVES
-#define JMHIP_PAIR_LIST_WAVES 2        /* list form: two waves per SIMD without spills measured 5 % faster than three with 55 spilled dwords */
-#endif
-template <bool LIST>
-__global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_pair_kernel(MeDev P0, const jmhip_me_mb *__restrict__ jobs, const int *__restrict__ job_index,
-                                                            jmhip_me_result *__restrict__ res, int n_items, const int *__restrict__ n_items_dev, int list_cap,
-                                                            const MeDev *__restrict__ P_dev)
+// One work item of me_int_pair_kernel: `word` is job index | representative partition << 24 | (all 41 predictors equal) << 30.
+// UNI is the compile-time form of bit 30. With ONE predictor both mv-bit counts are cheap where they are needed -- the vertical one is a
+// function of the candidate row (wave-uniform: scalar code), the horizontal one of the lane's column (constant over the walk) -- so the
+// UNI body stages no slot predictors, builds no bytab / bxtab, has no chg pass, and caches the mv cost in two registers (the 16-bit-shifted
+// cost every partition key adds, and the 16x16 key's unshifted one) instead of 22. The keys that reach best[] are the same numbers as in the
+// table body. UNI = false is the general body: per-partition tables, right for any predictors (JMHIP_ME_KERNEL=pair_tables clears bit 30 on
+// the host, so that one-predictor items take it too).
+template <bool UNI>
+__device__ __forceinline__ void pair_item(const MeDev &P, const jmhip_me_mb *__restrict__ jobs, jmhip_me_result *__restrict__ res,
+                                          uint32_t *swin, PairShared &S, const int word, const int tid)
 {
-  extern __shared__ __attribute__((aligned(16))) uint32_t swin[];      // 4 shifted window copies
-  __shared__ PairShared S;
-  if (LIST) n_items = jm_shard_slots(n_items_dev);                     // sharded list (jmhip_internal.h): virtual slots
-  for (int vblock = blockIdx.x; vblock < jm_xcd_grid(n_items); vblock += gridDim.x) {
-  if (LIST && vblock != (int)blockIdx.x) __syncthreads();              // the previous trip's last readers of S / swin
-  // the thread index is re-read (opaquely) in every trip: otherwise everything derived from it is hoisted out of the loop and kept alive across
-  // the whole body, which is already at the register budget of three waves per SIMD (93 dwords per lane went to scratch)
-  int tid = threadIdx.x;
-  if (LIST) asm volatile("" : "+v"(tid));
   const int lane = tid & 63, wave = tid >> 6;
-  // ... and the parameter block is re-read from memory in every trip (LIST): as a by-value argument its forty-odd scalars stay live across the loop
-  // and the scalar file overflows into vector registers
-  const MeDev *pp = P_dev;
-  if (LIST) asm volatile("" : "+s"(pp));
-  const MeDev &P = LIST ? *pp : P0;
-  const int item = jm_xcd_item_of(vblock, n_items);
-  if (item < 0) { if (LIST) continue; return; }
-  const int word = LIST ? jm_shard_entry(n_items_dev, job_index, list_cap, item) : job_index[item];
-  if (LIST && word < 0) continue;
-
   STAMP(0);
   const int mbi = word & 0xffffff, rep = (word >> 24) & 63;
-  const int uni = __builtin_amdgcn_readfirstlane((word >> 30) & 1);      // one predictor for all 41 partitions
   const jmhip_me_mb &job = jobs[mbi];
   const int mbx = job.mb_x, mby = job.mb_y;
   const int R = P.R, UW = 2 * R + 1, UH = UW;
   const int PITCH = P.win_pitch >> 2, CS = P.win_copy_stride, WROWS = UH + 15;
 
+  const int upx = job.pred_mv[rep][0], upy = job.pred_mv[rep][1];      // UNI: THE predictor
   int ucx, ucy;
-  search_center(P, job.pred_mv[rep][0], job.pred_mv[rep][1], &ucx, &ucy);
+  search_center(P, upx, upy, &ucx, &ucy);
   const int umin_x = ucx - R, umin_y = ucy - R;
   if (tid < JMHIP_NPART) { S.px[tid] = job.pred_mv[tid][0]; S.py[tid] = job.pred_mv[tid][1]; }
-  if (tid >= 64 && tid < 112) {                       // predictors in table-slot order, for the table build below
-    const int s = tid - 64, g = c_pair_g[s / 24][s % 24];
-    S.spx[s] = g >= 0 ? job.pred_mv[g][0] : SLOT_UNUSED;
-    S.spy[s] = g >= 0 ? job.pred_mv[g][1] : SLOT_UNUSED;
-  }
-  __syncthreads();                                    // before the window loads are issued: every lane waits for the job anyway
+  if (!UNI) {
+    if (tid >= 64 && tid < 112) {                     // predictors in table-slot order, for the table build below
+      const int s = tid - 64, g = c_pair_g[s / 24][s % 24];
+      S.spx[s] = g >= 0 ? job.pred_mv[g][0] : SLOT_UNUSED;
+      S.spy[s] = g >= 0 ? job.pred_mv[g][1] : SLOT_UNUSED;
+    }
+    __syncthreads();                                  // before the window loads are issued: every lane waits for the job anyway
+  }                                                   // (UNI: S.px / S.py are read only after the walk, behind the barriers below)
   if (tid < 64) S.cur[tid] = *reinterpret_cast<const uint32_t *>(P.cur + (size_t)(mby * 16 + (tid >> 2)) * P.W + mbx * 16 + (tid & 3) * 4);
 
   // ---- reference window (as me_int_fast_kernel): loads first, tables while they fly, four copies from registers
@@ -774,22 +759,16 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
   }
   // mv-bit tables, four slots (one dword) per item so that all 256 lanes work and a line of 48 slots is 12 stores:
   // 12 x (UH + UW) items; slot = half * 24 + local, unused slots hold 0
-  for (int e = tid; e < 12 * (UH + UW); e += 256) {
+  for (int e = tid; !UNI && e < 12 * (UH + UW); e += 256) {
     const bool isx = e >= 12 * UH;
     const int e2 = isx ? e - 12 * UH : e, line = e2 / 12, q = e2 - line * 12;
     const int v4 = 4 * ((isx ? umin_x : umin_y) + line);
     const int *sp = isx ? S.spx : S.spy;
     uint32_t w = 0;
-    if (uni) {                                          // every used slot holds the same count
-      const uint32_t b = (uint32_t)mvbits(v4 - sp[0]) * 0x01010101u;
 #pragma unroll
-      for (int k = 0; k < 4; k++) w |= sp[4 * q + k] == SLOT_UNUSED ? 0u : (b & (0xffu << (8 * k)));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int p = sp[4 * q + k];
-        w |= (p == SLOT_UNUSED ? 0u : (uint32_t)mvbits(v4 - p)) << (8 * k);
-      }
+    for (int k = 0; k < 4; k++) {
+      const int p = sp[4 * q + k];
+      w |= (p == SLOT_UNUSED ? 0u : (uint32_t)mvbits(v4 - p)) << (8 * k);
     }
     reinterpret_cast<uint32_t *>(isx ? S.bxtab[line] : S.bytab[line])[q] = w;
   }
@@ -828,7 +807,7 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
       swin[2 * CS + y * PITCH + xw] = __builtin_amdgcn_alignbyte(b, a, 2u);
       swin[3 * CS + y * PITCH + xw] = __builtin_amdgcn_alignbyte(b, a, 3u);
     }
-  if (tid < UH) {
+  if (!UNI && tid < UH) {
     unsigned m = (tid == 0);
     if (tid) {
       const uint32_t *a = reinterpret_cast<const uint32_t *>(S.bytab[tid]), *b = reinterpret_cast<const uint32_t *>(S.bytab[tid - 1]);
@@ -837,7 +816,7 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
     }
     S.chg[tid] = m;
   }
-  __syncthreads();
+  if (!UNI || !inside) __syncthreads();               // UNI inside the picture: nothing was written since the last barrier (`inside` is workgroup-uniform)
   STAMP(1);
 
   // ---- per-lane constants
@@ -856,7 +835,9 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
   unsigned best[PAIR_NK];
 #pragma unroll
   for (int j = 0; j < PAIR_NK; j++) best[j] = KEY_INVALID;
-  unsigned mvc[PAIR_NK];                             // cached (mv cost << 16); [21] (16x16) unshifted + bias
+  // cached (mv cost << 16); [21] (16x16) unshifted + bias. UNI: one cost serves every partition: [0] shifted, [1] the 16x16 form
+  constexpr int NMVC = UNI ? 2 : PAIR_NK;
+  unsigned mvc[NMVC];
 
   // one half candidate: sads of the 8 leaves (tie seeded), tree, partner exchange, 21 + 1 keys
   // mode 0: keep the keys in hold[] (even step of the row walk); 1: best = min3(best, hold, key) (odd step: one v_min3_u32 per two
@@ -883,11 +864,11 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
     ps[16] = ps[8] + ps[9]; ps[17] = ps[10] + ps[11];
     ps[18] = ps[16] + ps[17];
     ps[19] = quad_swap_add(ps[16]); ps[20] = quad_swap_add(ps[17]);
-    unsigned c0 = ((ps[19] >> 16) + (ps[20] >> 16)) + mvc[21];
+    unsigned c0 = ((ps[19] >> 16) + (ps[20] >> 16)) + mvc[NMVC - 1];
     if (zero_bonus) c0 -= (unsigned)w16;
     unsigned key[PAIR_NK];
 #pragma unroll
-    for (int j = 0; j < PAIR_NK - 1; j++) key[j] = ps[j] + mvc[j];
+    for (int j = 0; j < PAIR_NK - 1; j++) key[j] = ps[j] + mvc[UNI ? 0 : j];
     key[21] = (c0 << TIE_BITS) + tie;
 #pragma unroll
     for (int j = 0; j < PAIR_NK; j++) {
@@ -896,15 +877,15 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
       else best[j] = min(best[j], key[j]);
     }
   };
+  // UNI: the mv cost of a candidate from its two bit counts, mvbits(4 mvx - px) and mvbits(4 mvy - py) -- the entries bxtab[column][.]
+  // and bytab[row][.] hold in the table body -- by the expression load_mvc evaluates per partition
+  auto set_mvc = [&](unsigned bxbits, unsigned bybits) __attribute__((always_inline)) {
+    const unsigned prod = __umul24((unsigned)lam, bxbits + bybits);
+    mvc[0] = prod & 0xffff0000u;
+    mvc[NMVC - 1] = (prod >> 16) + (unsigned)w16;
+  };
   auto load_mvc = [&](int colx, int row) __attribute__((always_inline)) {
-    if (uni) {                                          // slot 0 of a half is a 4x4 leaf, always used
-      const unsigned prod = __umul24((unsigned)lam, (unsigned)S.bytab[row][half * 24] + (unsigned)S.bxtab[colx][half * 24]);
-      const unsigned hi = prod & 0xffff0000u;
-#pragma unroll
-      for (int j = 0; j < PAIR_NK - 1; j++) mvc[j] = hi;
-      mvc[PAIR_NK - 1] = (prod >> 16) + (unsigned)w16;
-      return;
-    }
+    if constexpr (!UNI) {                               // (mvc[] has two entries in the UNI body: nothing here is instantiated there)
     const uint2 *bt = reinterpret_cast<const uint2 *>(&S.bytab[row][half * 24]), *bxq = reinterpret_cast<const uint2 *>(&S.bxtab[colx][half * 24]);
     const uint2 b0 = bt[0], b1 = bt[1], b2 = bt[2], x0 = bxq[0], x1 = bxq[1], x2 = bxq[2];
     const uint32_t byp[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y}, bxp[6] = {x0.x, x0.y, x1.x, x1.y, x2.x, x2.y};
@@ -919,6 +900,7 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
           mvc[j] = j < PAIR_NK - 1 ? (prod & 0xffff0000u) : ((prod >> 16) + (unsigned)w16);
         }
       }
+    }
     }
   };
 
@@ -937,6 +919,8 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
 #pragma unroll
     for (int j = 0; j < 15; j++) { const uint32_t *wp = lbase + (r0 + j) * PITCH; win[j][0] = wp[0]; win[j][1] = wp[1]; }
     unsigned mnext = 0;
+    const unsigned bxbits = (unsigned)mvbits(4 * mvx - upx);      // UNI: this lane's horizontal bit count, for the whole walk
+    int bylast = -1;                                              // UNI: the vertical bit count mvc[] was made with (scalar; none yet)
     auto step = [&](auto ttc, int t0) __attribute__((always_inline)) {
       constexpr int tt = decltype(ttc)::value;
       const int t = t0 + tt;
@@ -944,7 +928,10 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
       const int row = r0 + t;
       { const uint32_t *wp = lbase + (row + 15) * PITCH; constexpr int sl = (tt + 15) & 15; win[sl][0] = wp[0]; win[sl][1] = wp[1]; }
       const int mvy = umin_y + row, dy = mvy - ucy;
-      {
+      if (UNI) {                                        // the row is wave-uniform: bit count and refresh test in scalar code
+        const int bybits = __builtin_amdgcn_readfirstlane(mvbits(4 * mvy - upy));
+        if (bybits != bylast) { bylast = bybits; set_mvc(bxbits, (unsigned)bybits); }
+      } else {
         const unsigned m = (t == 0) ? 1u : mnext;
         mnext = S.chg[min(row + 1, UH - 1)];
         if (__builtin_amdgcn_readfirstlane(m)) load_mvc(col, row);
@@ -971,7 +958,7 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
   }
 
   STAMP(3);
-  // ---- columns beyond 64: one candidate per lane pair, fresh window rows, mv costs straight from the tables
+  // ---- columns beyond 64: one candidate per lane pair, fresh window rows, mv costs straight from the tables (UNI: from the bit counts)
   {
     const int nrc = UW - 32 * NG, nrest = nrc * UH;
     for (int c = tid >> 1; c < nrest; c += 128) {
@@ -983,7 +970,8 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
       uint32_t w[16][2];
 #pragma unroll
       for (int r = 0; r < 16; r++) { w[r][0] = wrow[r * PITCH]; w[r][1] = wrow[r * PITCH + 1]; }
-      load_mvc(ax, ay);
+      if (UNI) set_mvc((unsigned)mvbits(4 * cmx - upx), (unsigned)mvbits(4 * cmy - upy));
+      else load_mvc(ax, ay);
       evaluate(std::integral_constant<int, 2>{}, w, 0, tie, quirk00 && 4 * (mbx * 16 + cmx) == mbx * 16 && 4 * (mby * 16 + cmy) == mby * 16);
     }
   }
@@ -1032,6 +1020,42 @@ __global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_
     }
   }
   STAMP(6);
+}
+
+// LIST: the work items are a device-resident list whose LENGTH is device-resident too (*n_items_dev; the slice search's relaxation sweeps,
+// me_xslice.hip, build it on the device and must not wait for the host): a fixed grid strides over it, one item per trip.
+#ifndef JMHIP_PAIR_LIST_WAVES
+#define JMHIP_PAIR_LIST_WAVES 2        /* list form: two waves per SIMD without spills measured 5 % faster than three with 55 spilled dwords */
+#endif
+template <bool LIST>
+__global__ __launch_bounds__(256, LIST ? JMHIP_PAIR_LIST_WAVES : 3) void me_int_pair_kernel(MeDev P0, const jmhip_me_mb *__restrict__ jobs, const int *__restrict__ job_index,
+                                                            jmhip_me_result *__restrict__ res, int n_items, const int *__restrict__ n_items_dev, int list_cap,
+                                                            const MeDev *__restrict__ P_dev)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t swin[];      // 4 shifted window copies
+  __shared__ PairShared S;
+  if (LIST) n_items = jm_shard_slots(n_items_dev);                     // sharded list (jmhip_internal.h): virtual slots
+  for (int vblock = blockIdx.x; vblock < jm_xcd_grid(n_items); vblock += gridDim.x) {
+  if (LIST && vblock != (int)blockIdx.x) __syncthreads();              // the previous trip's last readers of S / swin
+  // the thread index is re-read (opaquely) in every trip: otherwise everything derived from it is hoisted out of the loop and kept alive across
+  // the whole body, which is already at the register budget of three waves per SIMD (93 dwords per lane went to scratch)
+  int tid = threadIdx.x;
+  if (LIST) asm volatile("" : "+v"(tid));
+  // ... and the parameter block is re-read from memory in every trip (LIST): as a by-value argument its forty-odd scalars stay live across the loop
+  // and the scalar file overflows into vector registers
+  const MeDev *pp = P_dev;
+  if (LIST) asm volatile("" : "+s"(pp));
+  const MeDev &P = LIST ? *pp : P0;
+  const int item = jm_xcd_item_of(vblock, n_items);
+  if (item < 0) { if (LIST) continue; return; }
+  const int word = LIST ? jm_shard_entry(n_items_dev, job_index, list_cap, item) : job_index[item];
+  if (LIST && word < 0) continue;
+
+  // bit 30: one predictor for all 41 partitions. Wave-uniform, so a list may mix both kinds of item in one launch; the kernel's register
+  // allocation is the larger of the two bodies'
+  const int uni = __builtin_amdgcn_readfirstlane((word >> 30) & 1);
+  if (uni) pair_item<true>(P, jobs, res, swin, S, word, tid);
+  else pair_item<false>(P, jobs, res, swin, S, word, tid);
   if (!LIST) break;
   }
 }
@@ -1443,11 +1467,18 @@ void jm_launch_me_pair_list(jmhip_ctx *c, const MeDev &P, const MeDev *P_dev, si
 // host mirror of search_center (mv-search.c:752-762) to size the LDS window
 constexpr int FAST_MAX_CENTRES = JMHIP_NPART;  // one walk per distinct centre always: a single macroblock in the union-window kernel is a 0.5 ms serial chain
 
-// JMHIP_ME_KERNEL=single selects the one-lane-per-candidate kernel (2R+1 >= 64 only); default: the pair-lane kernel (2R+1 >= 32)
+// JMHIP_ME_KERNEL=single selects the one-lane-per-candidate kernel (2R+1 >= 64 only); default (and any other value): the pair-lane kernel (2R+1 >= 32)
 static int me_use_pair_kernel()
 {
   const char *e = getenv("JMHIP_ME_KERNEL");         // read per call: tests switch it
   return e && !strcmp(e, "single") ? 0 : 1;
+}
+// JMHIP_ME_KERNEL=pair_tables: the pair-lane kernel with bit 30 of every work word clear, so that one-predictor items too take the table body
+// (A/B runs of the one-predictor body: same launch, same results)
+static int me_pair_tables_only()
+{
+  const char *e = getenv("JMHIP_ME_KERNEL");
+  return e && !strcmp(e, "pair_tables") ? 1 : 0;
 }
 // JMHIP_ME_KERNEL=pers selects the persistent, double-buffered form of the pair-lane kernel (me_int_pers_kernel): bit-exact, measured
 // 13 % SLOWER than the default at 1080p (0.303 vs 0.267 ms; DESIGN.md section 3 has the counters that say why) -- kept as the measured experiment
@@ -1529,6 +1560,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
   // kernels search and me_metric.hip refines
   const bool metric_path = metric_any && (eff.metric[0] != 0 || eff.chroma_me != 0 || wide);
   if (resident && metric_path != c->me_last_metric_path) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: resident jobs need the metric path of the call that uploaded them");
+  const bool tables_only = me_pair_tables_only();
   for (int i = 0; i < n && !resident; i++) {
     const jmhip_me_mb &m = mbs[i];
     if (m.mb_x < 0 || m.mb_x >= c->mbw || m.mb_y < 0 || m.mb_y >= c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: macroblock outside the picture");
@@ -1559,7 +1591,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
     }
     if (fast) {
       // bit 30: all 41 predictors of the macroblock are equal (the metric's workload; smooth motion in JM's own fields): one mv cost serves every partition
-      bool uni = true;
+      bool uni = !tables_only;
       for (int p = 1; p < JMHIP_NPART && uni; p++) uni = m.pred_mv[p][0] == m.pred_mv[0][0] && m.pred_mv[p][1] == m.pred_mv[0][1];
       for (int g = 0; g < ng; g++) c->me_fast_idx.push_back(i | (reps[g] << 24) | (uni ? 1 << 30 : 0));
     }
