@@ -44,6 +44,7 @@ extern "C" int jmhip_sizeof(int which)
   case 30: return (int)sizeof(jmhip_bipred_chain_job);
   case 31: return (int)sizeof(jmhip_bipred_chain_params);
   case 32: return (int)sizeof(jmhip_bipred_chain_result);
+  case 33: return (int)sizeof(jmhip_bipred_surface_job);
   default: return -1;
   }
 }
@@ -128,6 +129,7 @@ extern "C" void jmhip_ctx_destroy(jmhip_ctx *c)
   for (auto e : c->pin_evt) (void)hipEventDestroy(e);
   (void)hipFree(c->stage_dev); (void)hipFree(c->me_jobs_dev); (void)hipFree(c->me_res_dev); (void)hipFree(c->ref_ptrs_dev); (void)hipFree(c->me_idx_dev); (void)hipFree(c->surf_dev); (void)hipFree(c->surf_jobs_dev);
   (void)hipFree(c->bic_jobs_dev); (void)hipFree(c->bic_res_dev);
+  (void)hipFree(c->bis_dev); (void)hipFree(c->bis_jobs_dev);
   (void)hipFree(c->tq_jobs_dev); (void)hipFree(c->tq_res_dev); (void)hipFree(c->tq_quant_dev);
   (void)hipFree(c->fr_bi); (void)hipFree(c->fr_rec); (void)hipFree(c->fr_rec8); (void)hipFree(c->fr_blk_ref); (void)hipFree(c->fr_jobs_y); (void)hipFree(c->fr_jobs_c); (void)hipFree(c->fr_res_y); (void)hipFree(c->fr_res_c);
   jm_slice_state_free(c);

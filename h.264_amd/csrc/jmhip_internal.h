@@ -49,6 +49,7 @@ struct jmhip_ctx {
   std::vector<int> me_fast_idx, me_gen_idx;                           // reference slots used by the last ME call
   void *surf_dev = nullptr, *surf_jobs_dev = nullptr; size_t surf_cap = 0, surf_jobs_cap = 0;   // jmhip_distortion_surface
   void *bic_jobs_dev = nullptr, *bic_res_dev = nullptr; size_t bic_cap = 0;                       // jmhip_bipred_chain: jobs / results, grown on demand
+  void *bis_dev = nullptr, *bis_jobs_dev = nullptr; size_t bis_cap = 0, bis_jobs_cap = 0;         // jmhip_bipred_surface: surfaces / jobs, grown on demand
   void *ref_ptrs_dev = nullptr;                       // [0..31] integer recon, [32..63] quarter-pel plane stacks
   // jmhip_recon_to_ref swaps plane pointers; the one table entry that changes is written by the next kernel that can carry it
   // (interp_luma, which every pipeline launches next) instead of a launch of its own; jm_ensure_ref_table flushes it otherwise

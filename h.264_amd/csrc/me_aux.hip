@@ -3,6 +3,7 @@
 //   surface_kernel<K>    every integer displacement in early-exit granularity, for EPZS / UMHexagonS (jmhip_distortion_surface)
 //   bipred_kernel        FullPelBlockMotionBiPred / SubPelBlockSearchBiPred                          (jmhip_bipred_search)
 //   bipred_chain_kernel  the bi-predictive refinement chain of BlockMotionSearch, one launch per chain     (jmhip_bipred_chain)
+//   bipred_surface_kernel<K>  the bi-predicted block at every integer displacement, same granularity, for the bi-pred walks (jmhip_bipred_surface)
 //   predcost_kernel      TransformDecision / GetSkipCostMB / BIDPartitionCost residual costs         (jmhip_pred_cost_batch)
 #include "me_common.h"
 
@@ -326,6 +327,60 @@ __device__ __forceinline__ void bi_stage_cur(const BiDev &B, BiLds &L, int ox, i
   }
 }
 
+// the (UW + 15)^2 window of a swept picture whose top-left sample is (bx, by), per-sample clamp on the integer plane, one 32-bit word per store
+__device__ __forceinline__ void bi_stage_window(const BiDev &B, uint8_t *smem, const uint8_t *ref, int bx, int by, int UW, int pitch)
+{
+  for (int d = threadIdx.x; d < (pitch >> 2) * (UW + 15); d += 256) {
+    const int y = d / (pitch >> 2), xw = d - y * (pitch >> 2);
+    const uint8_t *row = ref + (size_t)clampi(by + y, 0, B.H - 1) * B.W;
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) v |= (uint32_t)row[clampi(bx + xw * 4 + k, 0, B.W - 1)] << (8 * k);
+    *reinterpret_cast<uint32_t *>(smem + (size_t)y * pitch + xw * 4) = v;
+  }
+}
+
+// the fixed 16x16 block of picture 1 whose top-left sample is (fx, fy), clamped the same way
+__device__ __forceinline__ void bi_stage_fixed(const BiDev &B, BiLds &L, const uint8_t *ref, int fx, int fy)
+{
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    const int r = tid >> 2, k = tid & 3;
+    const uint8_t *row = ref + (size_t)clampi(fy + r, 0, B.H - 1) * B.W;
+    uint32_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) v |= (uint32_t)row[clampi(fx + k * 4 + j, 0, B.W - 1)] << (8 * j);
+    L.fix[r][k] = v;
+  }
+}
+
+// HadamardSAD8x8 (me_distortion.c:258) in two steps: one row of current minus prediction (packed bytes, samples 0..3 / 4..7) through the
+// horizontal butterflies, then the vertical butterflies and the sum over the eight transformed rows
+__device__ __forceinline__ void had8_diff_row(uint32_t c0, uint32_t c1, uint32_t lo, uint32_t hi, int out[8])
+{
+  int row[8];
+#pragma unroll
+  for (int x = 0; x < 4; x++) { row[x] = (int)((c0 >> (8 * x)) & 255) - (int)((lo >> (8 * x)) & 255); row[4 + x] = (int)((c1 >> (8 * x)) & 255) - (int)((hi >> (8 * x)) & 255); }
+  had8(row);
+#pragma unroll
+  for (int x = 0; x < 8; x++) out[x] = row[x];
+}
+
+__device__ __forceinline__ int had8_cols_sad(const int m2[8][8])
+{
+  int s = 0;
+#pragma unroll
+  for (int x = 0; x < 8; x++) {
+    int col[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) col[r] = m2[r][x];
+    had8(col);
+#pragma unroll
+    for (int r = 0; r < 8; r++) s += iabs(col[r]);
+  }
+  return (s + 2) >> 2;
+}
+
 // FullPelBlockMotionBiPred (me_fullsearch.c:164): integer planes, per-sample clamp == UMV origin clamp on the 20-pel ring. Stages the window
 // of picture 2 round (mvx, mvy) and the fixed block of picture 1, evaluates the (2R+1)^2 candidates and returns to every thread the packed
 // minimum (cost << TIE_BITS | spiral position). L.cur must be staged (this function's first barrier publishes it); two barriers inside,
@@ -335,25 +390,9 @@ __device__ __forceinline__ unsigned bi_fullpel(const BiDev &B, BiLds &L, uint8_t
   const int tid = threadIdx.x;
   const int UW = 2 * R + 1;
   const int pitch = (UW + 15 + 3 + 4) & ~3;
-  const uint8_t *ref1 = B.ref_y[q.ref1], *ref2 = B.ref_y[q.ref2];
-  const int bx = ox + mvx0 - R, by = oy + mvy0 - R;
   if (tid == 0) L.best = 0xffffffffu;
-  for (int d = tid; d < (pitch >> 2) * (UW + 15); d += 256) {
-    const int y = d / (pitch >> 2), xw = d - y * (pitch >> 2);
-    const uint8_t *row = ref2 + (size_t)clampi(by + y, 0, B.H - 1) * B.W;
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) v |= (uint32_t)row[clampi(bx + xw * 4 + k, 0, B.W - 1)] << (8 * k);
-    *reinterpret_cast<uint32_t *>(smem + (size_t)y * pitch + xw * 4) = v;
-  }
-  if (tid < 64) {
-    const int r = tid >> 2, k = tid & 3;
-    const uint8_t *row = ref1 + (size_t)clampi(oy + q.smvy + r, 0, B.H - 1) * B.W;
-    uint32_t v = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) v |= (uint32_t)row[clampi(ox + q.smvx + k * 4 + j, 0, B.W - 1)] << (8 * j);
-    L.fix[r][k] = v;
-  }
+  bi_stage_window(B, smem, B.ref_y[q.ref2], ox + mvx0 - R, oy + mvy0 - R, UW, pitch);
+  bi_stage_fixed(B, L, B.ref_y[q.ref1], ox + q.smvx, oy + q.smvy);
   __syncthreads();
   const int c1 = mv_cost(B.lam_f, 4 * q.smvx - q.p1x, 4 * q.smvy - q.p1y);
   unsigned best = 0xffffffffu;
@@ -445,24 +484,9 @@ __device__ __forceinline__ void bi_subpel(const BiDev &B, BiLds &L, int ox, int 
           fetch_row(r2 + (size_t)r * B.Wp, 8, &b0, &b1);
           const uint32_t lo = bipel4(B, a0, b0), hi = bipel4(B, a1, b1);
           const uint32_t c0 = *reinterpret_cast<const uint32_t *>(&L.cur[byo + r][bxo]), c1 = *reinterpret_cast<const uint32_t *>(&L.cur[byo + r][bxo + 4]);
-          int row[8];
-#pragma unroll
-          for (int x = 0; x < 4; x++) { row[x] = (int)((c0 >> (8 * x)) & 255) - (int)((lo >> (8 * x)) & 255); row[4 + x] = (int)((c1 >> (8 * x)) & 255) - (int)((hi >> (8 * x)) & 255); }
-          had8(row);
-#pragma unroll
-          for (int x = 0; x < 8; x++) m2[r][x] = row[x];
+          had8_diff_row(c0, c1, lo, hi, m2[r]);
         }
-        int s = 0;
-#pragma unroll
-        for (int x = 0; x < 8; x++) {
-          int col[8];
-#pragma unroll
-          for (int r = 0; r < 8; r++) col[r] = m2[r][x];
-          had8(col);
-#pragma unroll
-          for (int r = 0; r < 8; r++) s += iabs(col[r]);
-        }
-        v = (s + 2) >> 2;
+        v = had8_cols_sad(m2);
       }
       atomicAdd(&L.satd[cand], v);
     }
@@ -691,6 +715,135 @@ extern "C" int jmhip_bipred_chain(jmhip_ctx *c, const jmhip_bipred_chain_params 
   bipred_chain_kernel<<<n, 256, lds, c->stream>>>(B, C, (const jmhip_bipred_chain_job *)c->bic_jobs_dev, (jmhip_bipred_chain_result *)c->bic_res_dev);
   JM_HIP_CHECK(c, hipGetLastError());
   JM_HIP_CHECK(c, hipMemcpyAsync(results, c->bic_res_dev, sizeof(jmhip_bipred_chain_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return JMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ bi-predictive distortion surfaces
+
+namespace {
+
+// One workgroup per job: the fixed 16x16 block of picture 1 and the (2R+16)^2 window of picture 2 are staged in LDS once (per-sample clamp
+// on both), lane <-> displacement. Every lane forms the bi-predicted block of its displacement and writes it in the layouts of
+// surface_kernel: KIND 0 the 64 four-sample row SADs (computeBiPredSAD1/2), KIND 1 the 16 4x4 and 4 8x8 Hadamard SADs (computeBiPredSATD1/2).
+template <int KIND>
+__global__ __launch_bounds__(256) void bipred_surface_kernel(BiDev B, const jmhip_bipred_surface_job *__restrict__ jobs, uint16_t *__restrict__ out)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ __attribute__((aligned(16))) BiLds L;
+  const jmhip_bipred_surface_job job = jobs[blockIdx.x];
+  const int tid = threadIdx.x, R = job.R, UW = 2 * R + 1;
+  const int pitch = (UW + 15 + 3 + 4) & ~3;
+  const int ox = job.mb_x * 16, oy = job.mb_y * 16;
+  B.wp = job.wp != 0; B.w1 = job.weight1; B.w2 = job.weight2; B.off = job.offset_bi; B.rnd = job.wp_round; B.den = job.wp_denom;
+  bi_stage_cur(B, L, ox, oy);
+  bi_stage_window(B, smem, B.ref_y[job.ref2], ox + job.cx - R, oy + job.cy - R, UW, pitch);
+  bi_stage_fixed(B, L, B.ref_y[job.ref1], ox + job.s_mv[0], oy + job.s_mv[1]);
+  __syncthreads();
+  constexpr int NV = KIND == JMHIP_SURFACE_SAD_ROWS ? 64 : 20;
+  uint16_t *o = out + (size_t)blockIdx.x * UW * UW * NV;
+  for (int c = tid; c < UW * UW; c += 256) {
+    const int ay = c / UW, ax = c - ay * UW;
+    const uint8_t *wrow = smem + (size_t)ay * pitch + (ax & ~3);
+    const unsigned sh = ax & 3;
+    uint32_t pr[16][4];                              // the bi-predicted 16x16 block at this displacement, packed bytes
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+      const uint32_t *wp = reinterpret_cast<const uint32_t *>(wrow + (size_t)r * pitch);
+      const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2], d3 = wp[3], d4 = wp[4];
+      pr[r][0] = bipel4(B, L.fix[r][0], __builtin_amdgcn_alignbyte(d1, d0, sh)); pr[r][1] = bipel4(B, L.fix[r][1], __builtin_amdgcn_alignbyte(d2, d1, sh));
+      pr[r][2] = bipel4(B, L.fix[r][2], __builtin_amdgcn_alignbyte(d3, d2, sh)); pr[r][3] = bipel4(B, L.fix[r][3], __builtin_amdgcn_alignbyte(d4, d3, sh));
+    }
+    uint32_t *o32 = reinterpret_cast<uint32_t *>(o + (size_t)c * NV);
+    if (KIND == JMHIP_SURFACE_SAD_ROWS) {
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const uint32_t *cw = reinterpret_cast<const uint32_t *>(&L.cur[r][0]);
+        const uint32_t s0 = __builtin_amdgcn_sad_u8(pr[r][0], cw[0], 0u), s1 = __builtin_amdgcn_sad_u8(pr[r][1], cw[1], 0u);
+        const uint32_t s2 = __builtin_amdgcn_sad_u8(pr[r][2], cw[2], 0u), s3 = __builtin_amdgcn_sad_u8(pr[r][3], cw[3], 0u);
+        o32[2 * r] = s0 | (s1 << 16); o32[2 * r + 1] = s2 | (s3 << 16);
+      }
+    } else {
+      uint32_t v4[16];
+#pragma unroll
+      for (int b = 0; b < 16; b++) {
+        const int y0 = (b >> 2) * 4, k = b & 3;
+        uint32_t c01[4], c23[4], rf[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) { c01[r] = L.c16[y0 + r][2 * k]; c23[r] = L.c16[y0 + r][2 * k + 1]; rf[r] = pr[y0 + r][k]; }
+        v4[b] = (uint32_t)satd4x4_packed(c01, c23, rf);
+      }
+#pragma unroll
+      for (int b = 0; b < 8; b++) o32[b] = v4[2 * b] | (v4[2 * b + 1] << 16);
+      uint32_t v8[4];
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const int y0 = (b >> 1) * 8, k = (b & 1) * 2;
+        int m2[8][8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+          const uint32_t *cw = reinterpret_cast<const uint32_t *>(&L.cur[y0 + r][0]);
+          had8_diff_row(cw[k], cw[k + 1], pr[y0 + r][k], pr[y0 + r][k + 1], m2[r]);
+        }
+        v8[b] = (uint32_t)had8_cols_sad(m2);
+      }
+      o32[8] = v8[0] | (v8[1] << 16); o32[9] = v8[2] | (v8[3] << 16);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int jmhip_bipred_surface(jmhip_ctx *c, int kind, const jmhip_bipred_surface_job *jobs, int n, uint16_t *out)
+{
+  if (!c || !jobs || !out || n <= 0) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: NULL/empty arguments") : JMHIP_ERR_ARG;
+  if (kind != JMHIP_SURFACE_SAD_ROWS && kind != JMHIP_SURFACE_SATD_BLOCKS) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: kind");
+  if (!c->has_cur) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: current picture not uploaded");
+  const int R = jobs[0].R;
+  if (R < 0) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: one range (0..64) per call");
+  for (int i = 0; i < n; i++) if (jobs[i].R != R) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: one range (0..64) per call");
+  const int UW = 2 * R + 1, nv = kind == JMHIP_SURFACE_SAD_ROWS ? 64 : 20;
+  const int pitch = (UW + 15 + 3 + 4) & ~3;
+  const size_t lds = (size_t)pitch * (UW + 15) + 16;
+  if (lds > 48 * 1024) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_surface: range too large for one LDS window");
+  if (R > 64) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: one range (0..64) per call");
+  for (int i = 0; i < n; i++) {
+    const jmhip_bipred_surface_job &j = jobs[i];
+    if (j.mb_x < 0 || j.mb_x >= c->mbw || j.mb_y < 0 || j.mb_y >= c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: macroblock outside the picture");
+    for (int k = 0; k < 2; k++) {
+      const int s = k ? j.ref2 : j.ref1;
+      if (s < 0 || s >= (int)c->refs.size() || !c->refs[s].has_pic) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: reference slot not uploaded");
+    }
+    if (j.cx < -4096 || j.cx > 4096 || j.cy < -4096 || j.cy > 4096) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: centre out of range");
+    for (int k = 0; k < 2; k++) if (j.s_mv[k] < -4096 || j.s_mv[k] > 4096) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: fixed vector out of range");
+    if (j.wp && (j.wp_denom < 0 || j.wp_denom > 15)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_surface: weight denominator");
+  }
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  int rc = jm_ensure_ref_table(c);
+  if (rc) return rc;
+  const size_t bytes = (size_t)n * UW * UW * nv * sizeof(uint16_t);
+  if (c->bis_cap < bytes) {
+    if (c->bis_dev) JM_HIP_CHECK(c, hipFree(c->bis_dev));
+    c->bis_dev = nullptr; c->bis_cap = 0;
+    if (hipMalloc(&c->bis_dev, bytes) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred surface array");
+    c->bis_cap = bytes;
+  }
+  if (c->bis_jobs_cap < (size_t)n) {
+    if (c->bis_jobs_dev) JM_HIP_CHECK(c, hipFree(c->bis_jobs_dev));
+    c->bis_jobs_dev = nullptr; c->bis_jobs_cap = 0;
+    if (hipMalloc(&c->bis_jobs_dev, sizeof(jmhip_bipred_surface_job) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred surface jobs");
+    c->bis_jobs_cap = (size_t)n;
+  }
+  BiDev B{};
+  B.W = c->W; B.H = c->H; B.Wp = c->Wp; B.Hp = c->Hp; B.cur = c->cur_y;
+  B.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->bis_jobs_dev, jobs, sizeof(jmhip_bipred_surface_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  jm_stage_begin(c, JMHIP_STAGE_ME_INT);
+  if (kind == JMHIP_SURFACE_SAD_ROWS) bipred_surface_kernel<JMHIP_SURFACE_SAD_ROWS><<<n, 256, lds, c->stream>>>(B, (const jmhip_bipred_surface_job *)c->bis_jobs_dev, (uint16_t *)c->bis_dev);
+  else bipred_surface_kernel<JMHIP_SURFACE_SATD_BLOCKS><<<n, 256, lds, c->stream>>>(B, (const jmhip_bipred_surface_job *)c->bis_jobs_dev, (uint16_t *)c->bis_dev);
+  jm_stage_end(c, JMHIP_STAGE_ME_INT);
+  JM_HIP_CHECK(c, hipGetLastError());
+  JM_HIP_CHECK(c, hipMemcpyAsync(out, c->bis_dev, bytes, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }

@@ -133,6 +133,8 @@ PREDCOST_JOB_DTYPE = np.dtype([("mb_x", "<i2"), ("mb_y", "<i2"), ("blocks", "<u2
                                ("w0", "<i2", (16,)), ("w1", "<i2", (16,)), ("off", "<i2", (16,))])
 SURFACE_JOB_DTYPE = np.dtype([("mb_x", "<i2"), ("mb_y", "<i2"), ("ref", "<i2"), ("R", "<i2"), ("cx", "<i2"), ("cy", "<i2"),
                               ("wp", "<i2"), ("weight", "<i2"), ("offset", "<i2"), ("wp_round", "<i2"), ("wp_denom", "<i2"), ("pad", "<i2")])
+BIPRED_SURFACE_JOB_DTYPE = np.dtype([("mb_x", "<i2"), ("mb_y", "<i2"), ("ref1", "<i2"), ("ref2", "<i2"), ("s_mv", "<i2", (2,)), ("R", "<i2"), ("cx", "<i2"), ("cy", "<i2"),
+                                     ("wp", "<i2"), ("weight1", "<i2"), ("weight2", "<i2"), ("offset_bi", "<i2"), ("wp_round", "<i2"), ("wp_denom", "<i2"), ("pad", "<i2")])
 DEBLOCK_MB_DTYPE = np.dtype([("intra", "u1"), ("qp", "u1"), ("qpc", "u1", (2,)), ("disable_idc", "u1"), ("alpha_c0_offset", "i1"), ("beta_offset", "i1"),
                              ("transform_8x8", "u1"), ("avail_a", "u1"), ("avail_b", "u1"), ("cbp_blk", "<u2")])
 DEBLOCK_BLK_DTYPE = np.dtype([("mv", "<i2", (2, 2)), ("ref_id", "<i8", (2,))])
@@ -206,6 +208,7 @@ def load_library():
     lib.jmhip_distortion_surface.argtypes = [vp, ip, vp, ip, vp]
     lib.jmhip_bipred_search.argtypes = [vp, C.POINTER(BipredParams), vp, ip, vp]
     lib.jmhip_bipred_chain.argtypes = [vp, C.POINTER(BipredChainParams), vp, ip, vp]
+    lib.jmhip_bipred_surface.argtypes = [vp, ip, vp, ip, vp]
     lib.jmhip_tq_batch.argtypes = [vp, ip, ip, vp, ip, vp, ip, vp]
     lib.jmhip_flat_quant.argtypes = [vp, ip, ip, ip]
     lib.jmhip_flat_quant.restype = None
@@ -258,7 +261,7 @@ def load_library():
     for which, dt in ((0, ME_MB_DTYPE), (1, ME_RESULT_DTYPE), (2, QUANT_DTYPE), (3, TQ_JOB_DTYPE), (4, TQ_RESULT_DTYPE),
                       (5, DIST_JOB_DTYPE), (8, MB_MODE_DTYPE), (9, SURFACE_JOB_DTYPE), (10, BIPRED_JOB_DTYPE), (11, BIPRED_RESULT_DTYPE), (13, PREDCOST_JOB_DTYPE),
                       (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE), (24, MB_RESIDUAL422_DTYPE),
-                      (30, BIPRED_CHAIN_JOB_DTYPE), (32, BIPRED_CHAIN_RESULT_DTYPE)):
+                      (30, BIPRED_CHAIN_JOB_DTYPE), (32, BIPRED_CHAIN_RESULT_DTYPE), (33, BIPRED_SURFACE_JOB_DTYPE)):
         if lib.jmhip_sizeof(which) != dt.itemsize:
             raise JmhipError("binding layout mismatch for struct %d: C %d vs numpy %d" % (which, lib.jmhip_sizeof(which), dt.itemsize))
     if lib.jmhip_sizeof(6) != C.sizeof(MeParams) or lib.jmhip_sizeof(7) != C.sizeof(Config) or lib.jmhip_sizeof(12) != C.sizeof(BipredParams) or \
@@ -568,6 +571,15 @@ class Context:
         shape = (len(jobs), uw, uw, 16, 4) if kind == "sad_rows" else (len(jobs), uw, uw, 20)
         out = np.zeros(shape, dtype=np.uint16)
         self._chk(self.lib.jmhip_distortion_surface(self.h, 0 if kind == "sad_rows" else 1, _ptr(jobs), len(jobs), _ptr(out)), "jmhip_distortion_surface")
+        return out
+
+    def bipred_surface(self, kind, jobs):
+        """jmhip_bipred_surface: the bi-predicted block of every integer displacement; shapes as distortion_surface."""
+        jobs = np.ascontiguousarray(jobs, dtype=BIPRED_SURFACE_JOB_DTYPE)
+        uw = 2 * int(jobs[0]["R"]) + 1
+        shape = (len(jobs), uw, uw, 16, 4) if kind == "sad_rows" else (len(jobs), uw, uw, 20)
+        out = np.zeros(shape, dtype=np.uint16)
+        self._chk(self.lib.jmhip_bipred_surface(self.h, 0 if kind == "sad_rows" else 1, _ptr(jobs), len(jobs), _ptr(out)), "jmhip_bipred_surface")
         return out
 
     def distortion_batch(self, jobs):

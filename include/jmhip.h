@@ -302,6 +302,28 @@ typedef struct {
 int jmhip_bipred_chain(jmhip_ctx *ctx, const jmhip_bipred_chain_params *prm, const jmhip_bipred_chain_job *jobs, int n,
                        jmhip_bipred_chain_result *results);
 
+/* Bi-predictive distortion SURFACES for the host-driven bi-pred walks of the 16x16 block (EPZSBiPredBlockMotionSearch src/me_epzs.c:1971,
+ * UMHEXBipredIntegerPelBlockMotionSearch src/me_umhex.c:916, smpUMHEXBipredIntegerPelBlockMotionSearch src/me_umhexsmp.c:818): the block of
+ * picture ref1 at the FIXED vector s_mv is averaged ((a + b + 1) >> 1: computeBiPredSAD1 / SATD1, src/me_distortion.c:482, :824) or weight-combined
+ * (wp != 0: clip1(((weight1*a + weight2*b + 2*wp_round) >> (wp_denom + 1)) + offset_bi), computeBiPredSAD2 / SATD2 :556, :907) with the block of
+ * picture ref2 at EVERY integer displacement (cx-R..cx+R, cy-R..cy+R), raster order (dy outer). `kind` and the output layouts are those of
+ * jmhip_distortion_surface (64 / 20 uint16 per displacement), so one replay of JM's early exits serves both. Both operands follow UMV access
+ * (= per-sample clamp on the integer plane). The weighted 8x8 entries are the Hadamard SADs of the straight 8x8 blocks, as the oracle's
+ * jmo_bipred_satd forms them: computeBiPredSATD2's 8x8 branch reads its source one sample early per row (:1021 does not advance src_line),
+ * which neither the oracle nor this entry restates -- a binding must not answer weighted 8x8-transform calls from this surface.
+ * One R per call; R < 0 or mixed: JMHIP_ERR_ARG; an R whose window exceeds the LDS limit of jmhip_distortion_surface: JMHIP_ERR_UNSUPPORTED;
+ * any other R above 64: JMHIP_ERR_ARG. |cx|, |cy|, |s_mv| <= 4096. */
+typedef struct {
+  int16_t mb_x, mb_y;
+  int16_t ref1, ref2;       /* slots: FIXED block (listX[list][ref]) / SWEPT picture (listX[list^1][0]) */
+  int16_t s_mv[2];          /* the fixed block's vector, pel units */
+  int16_t R, cx, cy;        /* window of the swept picture: displacements (cx-R..cx+R, cy-R..cy+R), pel */
+  int16_t wp, weight1, weight2, offset_bi, wp_round, wp_denom;   /* wp != 0: computeBiPredSAD2 / SATD2 */
+  int16_t pad;
+} jmhip_bipred_surface_job;
+/* jobs / out: host arrays; the device arrays belong to the context and grow on demand. The call synchronises. */
+int jmhip_bipred_surface(jmhip_ctx *ctx, int kind, const jmhip_bipred_surface_job *jobs, int n, uint16_t *out);
+
 /* SubPelBlockMotionSearch alone (src/me_fullsearch.c:341): results[i].mv_int[p] is the INPUT (integer vector in pel
  * units, as FullPel/FastFull left it), results[i].mv/cost[p] the output. Same params/jobs as jmhip_me_frame. With
  * metric_set and equal metrics at the integer and half-pel level, results[i].cost_int[p] is an input too: the min_mcost the
@@ -738,7 +760,7 @@ int jmhip_ref_unpack_bands(jmhip_ctx *ctx, int ref, const void *chunks_device, i
  * 8 jmhip_mb_mode, 9 jmhip_surface_job, 10 jmhip_bipred_job, 11 jmhip_bipred_result, 12 jmhip_bipred_params, 13 jmhip_predcost_job,
  * 14 jmhip_deblock_mb, 15 jmhip_deblock_blk, 16 jmhip_deblock_params, 17 jmhip_slice_params, 18 jmhip_mb_inter, 19 jmhip_frame_wp,
  * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8, 24 jmhip_mb_residual422 (25..29: none, -1),
- * 30 jmhip_bipred_chain_job, 31 jmhip_bipred_chain_params, 32 jmhip_bipred_chain_result. */
+ * 30 jmhip_bipred_chain_job, 31 jmhip_bipred_chain_params, 32 jmhip_bipred_chain_result, 33 jmhip_bipred_surface_job. */
 int jmhip_sizeof(int which);
 
 /* Flat (no scaling matrix) tables: CalculateQuantParam / CalculateQuant8Param (src/q_matrix.c:451,590) and

@@ -35,6 +35,9 @@
  *        FullPelBlockMotionBiPred call runs jmhip_bipred_chain, and the following FullPelBlockMotionBiPred / SubPelBlockSearchBiPred calls of
  *        the same macroblock and list are answered from its trace after checking that JM passes the recorded inputs; on a mismatch the trace
  *        is dropped and the call takes the per-call device path.
+ * 0x40000 (opt-in) bi-predictive distortion surfaces for the bi-pred walks of EPZS / UMHexagonS / simplified UMHexagonS (16x16 block): the walk stays
+ *        JM's code, and its computeBiPredSAD1/2 / computeBiPredSATD1/2 calls at integer positions are answered, partial sums included, from one
+ *        jmhip_bipred_surface per (macroblock, pictures, fixed vector, weights).
  * 0x8000 the sub-pel planes stay on the device until JM is about to read them: getSubImagesLuma / getSubImagesChroma still upload the finished picture
  *        and build the planes, but only the integer plane (which JM's weighted-prediction estimation reads) crosses back at once; the other planes
  *        of a picture are fetched into JM's rows the first time a call is FORWARDED to JM code that reads reference planes (JM's own
@@ -71,7 +74,7 @@ extern const int LEVELMVLIMIT[17][6];
 extern int *mvbits;                       /* src/mv-search.c:59 */
 
 enum { S_LUMA, S_CHROMA, S_FULL, S_SUB, S_FAST, S_D4, S_D8, S_D16, S_DCR, S_WALK, S_SAD, S_SATD, S_BIFULL, S_BISUB, S_TDEC, S_SKIPC, S_BIDC, S_DEBLOCK, S_SLICE, S_BMS,
-       S_FRAME, S_D4R, S_DCRR, S_LPRED, S_CPRED, S_LAZY, S_D8R, S_LPREDC, S_CHAIN, S_CHAINC, S_COUNT };
+       S_FRAME, S_D4R, S_DCRR, S_LPRED, S_CPRED, S_LAZY, S_D8R, S_LPREDC, S_CHAIN, S_CHAINC, S_BIWALK, S_BIDIST, S_COUNT };
 static const char *s_names[S_COUNT] = { "getSubImagesLuma", "getSubImagesChroma", "FullPelBlockMotionSearch",
   "SubPelBlockMotionSearch", "FastFullPelBlockMotionSearch", "dct_4x4", "dct_8x8", "dct_16x16", "dct_chroma",
   "EPZS_UMHex_integer_walks", "computeSAD", "computeSATD", "FullPelBlockMotionBiPred", "SubPelBlockSearchBiPred",
@@ -79,7 +82,8 @@ static const char *s_names[S_COUNT] = { "getSubImagesLuma", "getSubImagesChroma"
   "P slices (one device call each)", "BlockMotionSearch",
   "frame stage of P slices", "dct_4x4 (slice records)", "dct_chroma (slice records)", "LumaPrediction (slice)", "ChromaPrediction4x4 (slice)", "sub-pel planes fetched on demand",
   "dct_8x8 (slice records)", "LumaPrediction (mode decision costs)",
-  "bi-pred chain", "bi-pred calls (chain)" };         /* chains run / dropped on a mismatch; calls answered from a chain's trace */
+  "bi-pred chain", "bi-pred calls (chain)",           /* chains run / dropped on a mismatch; calls answered from a chain's trace */
+  "EPZS_UMHex_bipred_walks", "computeBiPred" };       /* bi-pred walks recorded; computeBiPred* calls answered from a surface / forwarded to JM */
 static long n_dev[S_COUNT], n_fwd[S_COUNT];
 static double t_dev[S_COUNT], t_last[S_COUNT];             /* JMHIP_SHIM_STATS: wall seconds inside the coarse device-side hooks (planes, slice search, loop filter) */
 static int stats_on;
@@ -103,7 +107,7 @@ static void die(const char *what, int rc)
 }
 #define OK(call) do { int rc_ = (call); if (rc_) die(#call, rc_); } while (0)
 
-static long sl_slices(void), sl_passes(void);
+static long sl_slices(void), sl_passes(void), bi_surfaces(void);
 static void print_stats(void)
 {
   int i;
@@ -115,6 +119,7 @@ static void print_stats(void)
     fprintf(stderr, "\n");
   }
   if (sl_slices()) fprintf(stderr, "  slice binding: %ld slices, %ld kernel passes\n", sl_slices(), sl_passes());
+  if (bi_surfaces()) fprintf(stderr, "  bi-pred surfaces: %ld fetched\n", bi_surfaces());
 }
 
 int main(int argc, char **argv)
@@ -735,25 +740,27 @@ static const uint16_t *surface_at(int kind, int wp, int cand_x, int cand_y, int 
 
 /* computeSAD / computeSADWP (src/me_distortion.c:351, :413) and computeSATD / computeSATDWP (:657, :734) share their loop
  * structure and exits; the weighted forms only read weighted reference samples, which the weighted surface already holds. */
-static int sad_from_surface(const uint16_t *s, int bsy, int bsx, int min_mcost)
+/* (bx0, by0): the block's origin inside the macroblock. The bi-predictive forms (computeBiPredSAD1/2 :482, :556; computeBiPredSATD1/2 :824, :907)
+ * have the same loops and exits (:511, :603; :859, :893, :961, :1027) and replay through the same two functions. */
+static int sad_from_surface(const uint16_t *s, int bx0, int by0, int bsy, int bsx, int min_mcost)
 {
-  int mcost = 0, y, gx, g0 = walk.bx0 >> 2, g1 = (walk.bx0 + bsx) >> 2;
-  for (y = walk.by0; y < walk.by0 + bsy; y++) {       /* :364-375, the row-wise exit at :373 */
+  int mcost = 0, y, gx, g0 = bx0 >> 2, g1 = (bx0 + bsx) >> 2;
+  for (y = by0; y < by0 + bsy; y++) {                 /* :364-375, the row-wise exit at :373 */
     for (gx = g0; gx < g1; gx++) mcost += s[y * 4 + gx];
     if (mcost >= min_mcost) return mcost;
   }
   return mcost;
 }
 
-static int satd_from_surface(const uint16_t *s, int bsy, int bsx, int min_mcost)
+static int satd_from_surface(const uint16_t *s, int bx0, int by0, int bsy, int bsx, int min_mcost)
 {
   int mcost = 0, y, x;                                /* :669-731: sub-blocks y outer, x inner; exit on '>' */
   if (!test8x8transform) {
-    for (y = walk.by0; y < walk.by0 + bsy; y += 4)
-      for (x = walk.bx0; x < walk.bx0 + bsx; x += 4) { mcost += s[(y >> 2) * 4 + (x >> 2)]; if (mcost > min_mcost) return mcost; }
+    for (y = by0; y < by0 + bsy; y += 4)
+      for (x = bx0; x < bx0 + bsx; x += 4) { mcost += s[(y >> 2) * 4 + (x >> 2)]; if (mcost > min_mcost) return mcost; }
   } else {
-    for (y = walk.by0; y < walk.by0 + bsy; y += 8)
-      for (x = walk.bx0; x < walk.bx0 + bsx; x += 8) { mcost += s[16 + (y >> 3) * 2 + (x >> 3)]; if (mcost > min_mcost) return mcost; }
+    for (y = by0; y < by0 + bsy; y += 8)
+      for (x = bx0; x < bx0 + bsx; x += 8) { mcost += s[16 + (y >> 3) * 2 + (x >> 3)]; if (mcost > min_mcost) return mcost; }
   }
   return mcost;
 }
@@ -767,7 +774,7 @@ static int satd_from_surface(const uint16_t *s, int bsy, int bsx, int min_mcost)
       s = surface_at(KIND, WP, cand_x, cand_y, NV);                                                                   \
     if (!s) { if (!orig) orig = next_sym(#NAME); n_fwd[COUNTER]++; return orig(src_pic, bsy, bsx, min_mcost, cand_x, cand_y); } \
     n_dev[COUNTER]++;                                                                                                 \
-    return FROM(s, bsy, bsx, min_mcost);                                                                              \
+    return FROM(s, walk.bx0, walk.by0, bsy, bsx, min_mcost);                                                          \
   }
 DIST_HOOK(computeSAD,    JMHIP_SURFACE_SAD_ROWS,    0, 64, S_SAD,  sad_from_surface,  1)
 DIST_HOOK(computeSADWP,  JMHIP_SURFACE_SAD_ROWS,    1, 64, S_SAD,  sad_from_surface,  1)
@@ -801,6 +808,137 @@ int EPZSPelBlockMotionSearch(imgpel *cur_pic, short ref, int list, int list_offs
   }
 UMHEX_WALK(UMHEXIntegerPelBlockMotionSearch)
 UMHEX_WALK(smpUMHEXIntegerPelBlockMotionSearch)
+
+/* ------------------------------------------------------------------ EPZS / UMHexagonS bi-pred walks: JM's walker, the device's bi-predictive distortions (mask 0x40000) */
+
+/* EPZSBiPredBlockMotionSearch (src/me_epzs.c:1971), UMHEXBipredIntegerPelBlockMotionSearch (src/me_umhex.c:916) and
+ * smpUMHEXBipredIntegerPelBlockMotionSearch (src/me_umhexsmp.c:818) sweep the candidate of listX[list ^ 1][0] against the block of listX[list][ref]
+ * at the FIXED vector s_mv; each candidate is one computeBiPred call on the 16x16 block. The wrapper records what a surface depends on, JM's own
+ * walker runs, and the computeBiPred* definitions below answer from one jmhip_bipred_surface per (macroblock, pictures, s_mv, weights). The weights
+ * are read where JM's kernels read them (weight1 / weight2 / offsetBi, set by the walker before its first call). Forwarded to JM's own kernel: calls
+ * outside a recorded walk, sub-pel positions, another fixed position than the recorded one, displacements outside the window, the chroma term, SSE,
+ * FAST_ACCESS on a block that leaves the padded plane (JM then reads no clamped samples), and the weighted 8x8-transform SATD -- computeBiPredSATD2
+ * reads its source one sample early per row of an 8x8 block (src/me_distortion.c:1021), which the surface does not restate. */
+static struct { int on; imgpel *orig; int pic_x, pic_y, slot1, slot2, smx, smy, R, cx, cy; StorablePicture *p1, *p2; } biwalk;
+static struct { unsigned long serial; int mb_nr, slot1, smx, smy, cx, cy, R, wp, w1, w2, off, rnd, den; uint16_t *buf; } bisurf[2][MAX_SLOTS];   /* [kind][swept slot] */
+static long n_bisurf;                                 /* surfaces fetched (JMHIP_SHIM_STATS: the computeBiPred row's hook time is the time inside these calls) */
+
+static void biwalk_begin(imgpel *orig, short ref, int list, int pic_pix_x, int pic_pix_y, int blocktype, int smx, int smy, int pmx, int pmy)
+{
+  int s1 = -1, s2 = -1, R;
+  biwalk.on = 0;
+  if (!(shim_mask & 0x40000)) return;
+  if (blocktype == 1 && ref >= 0 && pic_pix_x == img->opix_x && pic_pix_y == img->opix_y && !img->mb_data[img->current_mb_nr].list_offset &&
+      !input->ChromaMEEnable && abs(smx) <= 4096 && abs(smy) <= 4096 && cur_ready()) {
+    biwalk.p1 = listX[list][ref]; biwalk.p2 = listX[list ^ 1][0];
+    s1 = slot_find(biwalk.p1); s2 = slot_find(biwalk.p2);
+  }
+  if (s1 < 0 || s2 < 0) { n_fwd[S_BIWALK]++; return; }   /* a walk whose distortions all stay in JM */
+  R = input->BiPredMESearchRange > 32 ? 32 : input->BiPredMESearchRange;
+  biwalk.on = 1; biwalk.orig = orig; biwalk.slot1 = s1; biwalk.slot2 = s2;
+  biwalk.pic_x = pic_pix_x; biwalk.pic_y = pic_pix_y; biwalk.smx = smx; biwalk.smy = smy;
+  /* centred as the uni-directional surfaces are: between the zero vector and the swept vector's predictor */
+  biwalk.R = R; biwalk.cx = iClip3(-R, R, pmx / 8); biwalk.cy = iClip3(-R, R, pmy / 8);
+  n_dev[S_BIWALK]++;
+}
+
+static long bi_surfaces(void) { return n_bisurf; }
+
+static int in_padded_plane(const StorablePicture *p, int xpos, int ypos)
+{
+  return xpos >= 0 && ypos >= 0 && xpos + 16 <= p->size_x_padded && ypos + 16 <= p->size_y_padded;
+}
+
+/* the surface of `kind` (+ weights) for the recorded walk; NULL if this pair of positions is not covered */
+static const uint16_t *bisurface_at(int kind, int wp, int x1, int y1, int x2, int y2, int nv)
+{
+  int ax, ay, UW = 2 * biwalk.R + 1, s = biwalk.slot2;
+  if (((x1 | y1 | x2 | y2) & 3) || ref_pic1_sub.luma != biwalk.p1->p_curr_img_sub || ref_pic2_sub.luma != biwalk.p2->p_curr_img_sub) return NULL;
+  if ((x1 >> 2) - IMG_PAD_SIZE - biwalk.pic_x != biwalk.smx || (y1 >> 2) - IMG_PAD_SIZE - biwalk.pic_y != biwalk.smy) return NULL;
+  if (bipred1_access_method == FAST_ACCESS && !in_padded_plane(biwalk.p1, x1 >> 2, y1 >> 2)) return NULL;
+  if (bipred2_access_method == FAST_ACCESS && !in_padded_plane(biwalk.p2, x2 >> 2, y2 >> 2)) return NULL;
+  ax = (x2 >> 2) - IMG_PAD_SIZE - biwalk.pic_x - biwalk.cx + biwalk.R; ay = (y2 >> 2) - IMG_PAD_SIZE - biwalk.pic_y - biwalk.cy + biwalk.R;
+  if (ax < 0 || ay < 0 || ax >= UW || ay >= UW) return NULL;
+  if (bisurf[kind][s].serial != pic_serial || bisurf[kind][s].mb_nr != img->current_mb_nr || !bisurf[kind][s].buf || bisurf[kind][s].slot1 != biwalk.slot1 ||
+      bisurf[kind][s].smx != biwalk.smx || bisurf[kind][s].smy != biwalk.smy || bisurf[kind][s].cx != biwalk.cx || bisurf[kind][s].cy != biwalk.cy ||
+      bisurf[kind][s].R != biwalk.R || bisurf[kind][s].wp != wp ||
+      (wp && (bisurf[kind][s].w1 != weight1 || bisurf[kind][s].w2 != weight2 || bisurf[kind][s].off != offsetBi || bisurf[kind][s].rnd != wp_luma_round ||
+              bisurf[kind][s].den != luma_log_weight_denom))) {
+    jmhip_bipred_surface_job job;
+    if (!bisurf[kind][s].buf || bisurf[kind][s].R != biwalk.R) {
+      free(bisurf[kind][s].buf);
+      bisurf[kind][s].buf = malloc((size_t)UW * UW * nv * sizeof(uint16_t));
+    }
+    memset(&job, 0, sizeof(job));
+    job.mb_x = img->opix_x >> 4; job.mb_y = img->opix_y >> 4; job.ref1 = biwalk.slot1; job.ref2 = s;
+    job.s_mv[0] = biwalk.smx; job.s_mv[1] = biwalk.smy; job.R = biwalk.R; job.cx = biwalk.cx; job.cy = biwalk.cy;
+    if (wp) { job.wp = 1; job.weight1 = weight1; job.weight2 = weight2; job.offset_bi = offsetBi; job.wp_round = wp_luma_round; job.wp_denom = luma_log_weight_denom; }
+    {
+      const double t0 = now_s();
+      OK(jmhip_bipred_surface(g, kind, &job, 1, bisurf[kind][s].buf));
+      t_last[S_BIDIST] = now_s() - t0; t_dev[S_BIDIST] += t_last[S_BIDIST]; n_bisurf++;
+    }
+    bisurf[kind][s].serial = pic_serial; bisurf[kind][s].mb_nr = img->current_mb_nr; bisurf[kind][s].slot1 = biwalk.slot1;
+    bisurf[kind][s].smx = biwalk.smx; bisurf[kind][s].smy = biwalk.smy; bisurf[kind][s].cx = biwalk.cx; bisurf[kind][s].cy = biwalk.cy; bisurf[kind][s].R = biwalk.R;
+    bisurf[kind][s].wp = wp; bisurf[kind][s].w1 = weight1; bisurf[kind][s].w2 = weight2; bisurf[kind][s].off = offsetBi;
+    bisurf[kind][s].rnd = wp_luma_round; bisurf[kind][s].den = luma_log_weight_denom;
+  }
+  return bisurf[kind][s].buf + ((size_t)ay * UW + ax) * nv;
+}
+
+#define BIDIST_HOOK(NAME, KIND, WP, NV, FROM, EXTRA)                                                                  \
+  int NAME(imgpel *src_pic, int bsy, int bsx, int min_mcost, int cand_x1, int cand_y1, int cand_x2, int cand_y2)       \
+  {                                                                                                                   \
+    static int (*orig)(imgpel *, int, int, int, int, int, int, int);                                                  \
+    const uint16_t *s = NULL;                                                                                         \
+    if (biwalk.on && src_pic == biwalk.orig && bsx == 16 && bsy == 16 && !ChromaMEEnable && (EXTRA))                  \
+      s = bisurface_at(KIND, WP, cand_x1, cand_y1, cand_x2, cand_y2, NV);                                             \
+    if (!s) {                                                                                                         \
+      if (!orig) orig = next_sym(#NAME);                                                                              \
+      if (shim_mask & 0x40000) n_fwd[S_BIDIST]++;                                                                     \
+      return orig(src_pic, bsy, bsx, min_mcost, cand_x1, cand_y1, cand_x2, cand_y2);                                  \
+    }                                                                                                                 \
+    n_dev[S_BIDIST]++;                                                                                                \
+    return FROM(s, 0, 0, bsy, bsx, min_mcost);                                                                        \
+  }
+BIDIST_HOOK(computeBiPredSAD1,  JMHIP_SURFACE_SAD_ROWS,    0, 64, sad_from_surface,  1)
+BIDIST_HOOK(computeBiPredSAD2,  JMHIP_SURFACE_SAD_ROWS,    1, 64, sad_from_surface,  1)
+BIDIST_HOOK(computeBiPredSATD1, JMHIP_SURFACE_SATD_BLOCKS, 0, 20, satd_from_surface, 1)
+BIDIST_HOOK(computeBiPredSATD2, JMHIP_SURFACE_SATD_BLOCKS, 1, 20, satd_from_surface, !test8x8transform)
+/* the SSE metric has no surface: JM's own kernels, counted */
+BIDIST_HOOK(computeBiPredSSE1,  0, 0, 0, sad_from_surface, 0)
+BIDIST_HOOK(computeBiPredSSE2,  0, 0, 0, sad_from_surface, 0)
+
+int EPZSBiPredBlockMotionSearch(imgpel *cur_pic, short ref, int list, int list_offset, char ***refPic, short ****tmp_mv,
+                                int pic_pix_x, int pic_pix_y, int blocktype, short *pred_mv1, short *pred_mv2, short mv[2], short s_mv[2],
+                                int search_range, int min_mcost, int lambda_factor)
+{
+  static int (*orig)(imgpel *, short, int, int, char ***, short ****, int, int, int, short *, short *, short *, short *, int, int, int);
+  int r;
+  if (!orig) orig = next_sym("EPZSBiPredBlockMotionSearch");
+  /* (on the sub-pel grid the walk's vectors are no pel vectors: every candidate would be forwarded anyway) */
+  if (!list_offset && !input->EPZSGrid && !input->EPZSSubPelGrid) biwalk_begin(cur_pic, ref, list, pic_pix_x, pic_pix_y, blocktype, s_mv[0], s_mv[1], pred_mv2[0], pred_mv2[1]);
+  r = orig(cur_pic, ref, list, list_offset, refPic, tmp_mv, pic_pix_x, pic_pix_y, blocktype, pred_mv1, pred_mv2, mv, s_mv, search_range, min_mcost, lambda_factor);
+  biwalk.on = 0;
+  return r;
+}
+
+#define UMHEX_BIWALK(NAME)                                                                                            \
+  int NAME(imgpel *cur_pic, short ref, int list, int pic_pix_x, int pic_pix_y, int blocktype, short pred_mv_x1,        \
+           short pred_mv_y1, short pred_mv_x2, short pred_mv_y2, short *mv_x, short *mv_y, short *s_mv_x,             \
+           short *s_mv_y, int search_range, int min_mcost, int lambda_factor)                                         \
+  {                                                                                                                   \
+    static int (*orig)(imgpel *, short, int, int, int, int, short, short, short, short, short *, short *, short *, short *, int, int, int); \
+    int r;                                                                                                            \
+    if (!orig) orig = next_sym(#NAME);                                                                                \
+    biwalk_begin(cur_pic, ref, list, pic_pix_x, pic_pix_y, blocktype, *s_mv_x, *s_mv_y, pred_mv_x2, pred_mv_y2);      \
+    r = orig(cur_pic, ref, list, pic_pix_x, pic_pix_y, blocktype, pred_mv_x1, pred_mv_y1, pred_mv_x2, pred_mv_y2, mv_x, mv_y, s_mv_x, s_mv_y, \
+             search_range, min_mcost, lambda_factor);                                                                 \
+    biwalk.on = 0;                                                                                                    \
+    return r;                                                                                                         \
+  }
+UMHEX_BIWALK(UMHEXBipredIntegerPelBlockMotionSearch)
+UMHEX_BIWALK(smpUMHEXBipredIntegerPelBlockMotionSearch)
 
 /* ------------------------------------------------------------------ RD-off mode-decision costs */
 
