@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "jmhip.h"
@@ -106,6 +107,21 @@ static inline int jm_fail(jmhip_ctx *ctx, int code, const char *msg)
   if (ctx) ctx->err = msg;
   return code;
 }
+
+// One device allocation and its byte count, freed with its owner (host code only; move-only). alloc() releases what it held first and leaves
+// it empty when the allocation fails. The slice-search states (me_wave.hip, me_xslice.hip) keep their buffers in these.
+struct DevBuf {
+  void *ptr = nullptr; size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept { swap(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }      // (o's destructor frees what this one held)
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (ptr) (void)hipFree(ptr); }
+  bool alloc(size_t n) { DevBuf().swap(*this); if (hipMalloc(&ptr, n) != hipSuccess) { ptr = nullptr; return false; } bytes = n; return true; }
+  template <class T> T *as() const { return static_cast<T *>(ptr); }
+  void swap(DevBuf &o) { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); }
+};
 
 // RAII-less stage timer: call begin before the launches of a stage and end after them.
 void jm_stage_begin(jmhip_ctx *ctx, int stage);

@@ -46,13 +46,13 @@ void build_part_table()
 
 
 __device__ __forceinline__ int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
-__device__ __forceinline__ int iabs(int x) { return x < 0 ? -x : x; }
+__host__ __device__ __forceinline__ int iabs(int x) { return x < 0 ? -x : x; }
 // mvbits[d] (mv-search.c:333-341): 1 for 0, 2*floor(log2|d|)+3 otherwise == 65 - 2*clz(|d|) with clz(0) = 32
 __device__ __forceinline__ int mvbits(int d) { return 65 - 2 * __clz(iabs(d)); }
 __device__ __forceinline__ int mv_cost(int lambda, int dx, int dy) { return (lambda * (mvbits(dx) + mvbits(dy))) >> 16; }
 
 // spiral_search index of offset (dx,dy), mv-search.c:366-393
-__device__ __forceinline__ int spiral_pos(int dx, int dy)
+__host__ __device__ __forceinline__ int spiral_pos(int dx, int dy)
 {
   const int adx = iabs(dx), ady = iabs(dy), l = max(adx, ady);
   if (l == 0) return 0;

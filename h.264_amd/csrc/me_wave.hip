@@ -2302,61 +2302,100 @@ __global__ void carry_check_kernel(const short *carry_in, const short *carry_out
   if (!same) atomicMin(&flags[1], r);
 }
 
+// EPZSMap / EPZSBlkCount for one search range: the map (16-bit stamps) and the search counter as the last slice left them (and where the
+// running call writes the next ones), the per-macroblock touch records and the scan's scratch
+struct EpMaps {
+  DevBuf map, map_next, count, count_next, first, last, alias_flag, nsearch, base, seg_last, seg_in, alias, alias_new, alias_n;
+  int cells = 0;
+  bool alloc(size_t nmb, int ncells)
+  {
+    const size_t nseg = (nmb + EP_SEG - 1) / EP_SEG;
+    cells = ncells;
+    return map.alloc(sizeof(uint16_t) * cells) && map_next.alloc(sizeof(uint16_t) * cells) && count.alloc(sizeof(uint32_t)) && count_next.alloc(sizeof(uint32_t)) &&
+           first.alloc(nmb * cells) && last.alloc(nmb * cells) && alias_flag.alloc(nmb) && nsearch.alloc(sizeof(uint16_t) * nmb) && base.alloc(sizeof(uint32_t) * (nmb + 1)) &&
+           seg_last.alloc(sizeof(uint32_t) * nseg * cells) && seg_in.alloc(sizeof(uint32_t) * nseg * cells) && alias.alloc(sizeof(unsigned long long) * EP_ALIAS_CAP) &&
+           alias_new.alloc(sizeof(unsigned long long) * EP_ALIAS_CAP) && alias_n.alloc(sizeof(int));
+  }
+};
+
+// Every buffer is a DevBuf: it is allocated in one place (alloc below, EpMaps::alloc, ensure_surfaces, ensure_tie_table), its size is written
+// there only (clears take buf.bytes) and it is freed with the state.
 struct SliceState {
-  int8_t *ref_idx = nullptr; short *mv = nullptr;
-  int *prog = nullptr, *flags = nullptr;
-  jmhip_mb_inter *out = nullptr;
-  int *ref8ts = nullptr;                       // [nmb][4] next to out (WaveDev.ref8ts); a slice call rewrites its own macroblocks only
-  int *ep_dist = nullptr; short *ep_motion = nullptr; short *ep_col = nullptr;        // row memories: [mbh + 1] stored rows (WaveDev)
-  // EPZSMap / EPZSBlkCount: the map (16-bit stamps) and the search counter as the last slice left them (and where the running call writes the
-  // next ones), the per-macroblock touch records and the scan's scratch
-  uint16_t *ep_map = nullptr, *ep_map_next = nullptr; uint32_t *ep_count = nullptr, *ep_count_next = nullptr; int ep_cells = 0;
-  uint8_t *ep_first = nullptr, *ep_last = nullptr, *ep_alias_flag = nullptr; uint16_t *ep_nsearch = nullptr;
-  uint32_t *ep_base = nullptr, *ep_seg_last = nullptr, *ep_seg_in = nullptr; unsigned long long *ep_alias = nullptr, *ep_alias_new = nullptr; int *ep_alias_n = nullptr;
+  DevBuf ref_idx, mv;                          // int8 [h4][w4], short [h4][w4][2]
+  DevBuf prog, flags;                          // int [mbh], int [4]
+  DevBuf out;                                  // jmhip_mb_inter [nmb]
+  DevBuf ref8ts;                               // int [nmb][4] next to out (WaveDev.ref8ts); a slice call rewrites its own macroblocks only
+  DevBuf ep_dist, ep_motion, ep_col;           // row memories: [mbh + 1] stored rows (WaveDev)
+  EpMaps ep;
   int ep_aliases = 0;                          // map tests of the last call answered from an old stamp
-  short *carry_mb = nullptr; uint8_t *chg[2] = {nullptr, nullptr};
-  unsigned long long *memo = nullptr;
-  uint16_t *tie_tab = nullptr; int tie_R = 0;
-  short *carry_in = nullptr, *carry_out = nullptr, *carry_slice = nullptr, *carry_slice_next = nullptr;
-  int *um_cost = nullptr, *um_cost_snap = nullptr;
-  uint16_t *surf = nullptr; size_t surf_rows = 0; int surf_n = 0, surf_refs = 0;
+  DevBuf carry_mb, chg[2];
+  DevBuf memo;
+  DevBuf tie_tab; int tie_R = 0;
+  DevBuf carry_in, carry_out, carry_slice, carry_slice_next;
+  DevBuf um_cost, um_cost_snap;
+  DevBuf surf; size_t surf_rows = 0; int surf_n = 0, surf_refs = 0;
   int passes = 0;
   bool has_col = false;
   int searched_from = 0, searched_to = 0;      // macroblocks [searched_from, searched_to) of the current picture have been searched (by slice calls in order)
   bool t8_any = false;                         // a slice of the current picture was searched with Transform8x8Mode: macroblocks may carry the 8x8-transform flag
   bool t8_all = false;                         // ... every slice of [searched_from, searched_to) was: ref8ts holds a reference for each of their blocks
+  bool alloc(const jmhip_ctx *c)               // what is sized by the picture alone
+  {
+    const size_t w4 = c->W / 4, h4 = c->H / 4, mbh = c->mbh, nmb = (size_t)c->mbw * c->mbh, carry = sizeof(short) * WR * CARRY * 2;
+    return ref_idx.alloc(w4 * h4) && mv.alloc(w4 * h4 * 4) && prog.alloc(sizeof(int) * mbh) && flags.alloc(sizeof(int) * 4) && out.alloc(sizeof(jmhip_mb_inter) * nmb) &&
+           ref8ts.alloc(sizeof(int) * 4 * nmb) && ep_dist.alloc(sizeof(int) * (mbh + 1) * 7 * w4) && ep_motion.alloc(sizeof(short) * (mbh + 1) * WR * 7 * 4 * w4 * 2) &&
+           carry_mb.alloc(carry * nmb) && chg[0].alloc(nmb) && chg[1].alloc(nmb) && memo.alloc(sizeof(unsigned long long) * nmb * WR) && ep_col.alloc(sizeof(short) * h4 * w4 * 2) &&
+           carry_in.alloc(carry * mbh) && carry_out.alloc(carry * mbh) && carry_slice.alloc(carry) && carry_slice_next.alloc(carry) &&
+           um_cost.alloc(sizeof(int) * 8 * h4 * w4) && um_cost_snap.alloc(sizeof(int) * 8 * h4 * w4);
+  }
+};
+
+// the environment's knobs of the driver, read once per call (a test or an experiment may change them between calls)
+struct SliceKnobs {
+  int relax_grid;                              // JMHIP_SLICE_GRID: workgroups of the relaxation sweeps (2048: two waves per SIMD at 256 VGPRs is all that can be resident); 0 under JMHIP_SLICE_SCHED=wave
+  int sweeps;                                  // JMHIP_SLICE_SWEEPS: cap on the relaxation sweeps of this file's kernels (a sweep costs >= one macroblock (1.2 ms), the walk 250+)
+  bool memo;                                   // JMHIP_SLICE_MEMO=0: no call records in the exhaustive searches' sweeps
+  // the walkers' sweep 0 searches the 16x16 mode only (JMHIP_SLICE_REDUCED0=0: a full sweep 0). Measured per new 1080p picture, bench clip: EPZS 32 / 23 / 55 -> 24 / 23 / 47 ms,
+  // UMHexagonS 19.5 / 19.5 / 38 -> 16 / 16.5 / 36 ms; the smooth clip within +-5 %
+  bool reduced0;
+  bool trace;                                  // JMHIP_SLICE_TRACE: a line on stderr per sweep and per EPZS map round
+  int debug;                                   // JMHIP_WAVE_DEBUG (WaveDev.debug)
+};
+
+// one jmhip_p_slice_search call: what its steps share
+struct SliceCall {
+  jmhip_ctx *c; const jmhip_slice_params *prm; SliceState *s;
+  SliceKnobs knobs;
+  int row_first, rows;                         // the macroblock rows the slice touches
+  bool exhaustive, epzs;
+  bool x_settled = false;                      // the sweeps over the frame kernels (me_xslice.hip) settled the slice: nothing is left for this file's kernels
+  bool settled = false;                        // the field is at its fixpoint under the current set of pre-marked EPZS map cells
+  int sweep_no = 0;                            // relaxation sweeps of this call so far (the changed-flag arrays alternate with it)
+  WaveDev D{};
+  std::vector<unsigned long long> ep_used;     // EPZS: the map tests this call's searches took as answered from an old stamp (sorted)
+  int sweep_frame_kernels(), ensure_surfaces(), ensure_tie_table(), prepare_epzs(), relax_to_fixpoint(), walk_coding_order(), epzs_alias_round(int round, bool *again), search_slice();
+  void fill_wave_dev();
+};
+
+// holds a stage of the timer open: every return out of the scope closes it
+struct StageScope {
+  jmhip_ctx *c; int stage;
+  StageScope(jmhip_ctx *ctx, int st) : c(ctx), stage(st) { jm_stage_begin(c, stage); }
+  ~StageScope() { jm_stage_end(c, stage); }
+  StageScope(const StageScope &) = delete;
+  StageScope &operator=(const StageScope &) = delete;
 };
 
 }  // namespace
 
-static void slice_state_release(SliceState *s)
-{
-  void *bufs[] = {s->ref_idx, s->mv, s->prog, s->flags, s->out, s->ref8ts, s->ep_dist, s->ep_motion, s->carry_mb, s->chg[0], s->chg[1], s->memo, s->tie_tab, s->ep_col, s->carry_in, s->carry_out,
-                  s->carry_slice, s->carry_slice_next, s->um_cost, s->um_cost_snap, s->surf, s->ep_map, s->ep_map_next, s->ep_count, s->ep_count_next, s->ep_first, s->ep_last,
-                  s->ep_alias_flag, s->ep_nsearch, s->ep_base, s->ep_seg_last, s->ep_seg_in, s->ep_alias, s->ep_alias_new, s->ep_alias_n};
-  for (void *b : bufs) if (b) (void)hipFree(b);
-  delete s;
-}
+static hipError_t fill(jmhip_ctx *c, const DevBuf &b, int byte) { return hipMemsetAsync(b.ptr, byte, b.bytes, c->stream); }
 
 // the state lives in the context as an opaque pointer (jmhip_internal.h: void *slice_state)
 static SliceState *slice_state(jmhip_ctx *c)
 {
   if (c->slice_state) return static_cast<SliceState *>(c->slice_state);
   SliceState *s = new SliceState();
-  const size_t w4 = c->W / 4, h4 = c->H / 4, nmb = (size_t)c->mbw * c->mbh;
-  bool ok = hipMalloc((void **)&s->ref_idx, w4 * h4) == hipSuccess && hipMalloc((void **)&s->mv, w4 * h4 * 4) == hipSuccess &&
-            hipMalloc((void **)&s->prog, sizeof(int) * c->mbh) == hipSuccess && hipMalloc((void **)&s->flags, sizeof(int) * 4) == hipSuccess &&
-            hipMalloc((void **)&s->out, sizeof(jmhip_mb_inter) * nmb) == hipSuccess && hipMalloc((void **)&s->ref8ts, sizeof(int) * 4 * nmb) == hipSuccess &&
-            hipMalloc((void **)&s->ep_dist, sizeof(int) * (c->mbh + 1) * 7 * w4) == hipSuccess &&
-            hipMalloc((void **)&s->ep_motion, sizeof(short) * (c->mbh + 1) * WR * 7 * 4 * w4 * 2) == hipSuccess &&
-            hipMalloc((void **)&s->carry_mb, sizeof(short) * nmb * WR * CARRY * 2) == hipSuccess &&
-            hipMalloc((void **)&s->chg[0], nmb) == hipSuccess && hipMalloc((void **)&s->chg[1], nmb) == hipSuccess &&
-            hipMalloc((void **)&s->memo, sizeof(unsigned long long) * nmb * WR) == hipSuccess &&
-            hipMalloc((void **)&s->ep_col, sizeof(short) * h4 * w4 * 2) == hipSuccess &&
-            hipMalloc((void **)&s->carry_in, sizeof(short) * c->mbh * WR * CARRY * 2) == hipSuccess && hipMalloc((void **)&s->carry_out, sizeof(short) * c->mbh * WR * CARRY * 2) == hipSuccess &&
-            hipMalloc((void **)&s->carry_slice, sizeof(short) * WR * CARRY * 2) == hipSuccess && hipMalloc((void **)&s->carry_slice_next, sizeof(short) * WR * CARRY * 2) == hipSuccess &&
-            hipMalloc((void **)&s->um_cost, sizeof(int) * 8 * h4 * w4) == hipSuccess && hipMalloc((void **)&s->um_cost_snap, sizeof(int) * 8 * h4 * w4) == hipSuccess;
-  if (!ok || hipMemset(s->ref8ts, 0xff, sizeof(int) * 4 * nmb) != hipSuccess) { slice_state_release(s); return nullptr; }      // nothing half-allocated stays behind: the call fails with NOMEM and may be retried
+  if (!s->alloc(c) || hipMemset(s->ref8ts.ptr, 0xff, s->ref8ts.bytes) != hipSuccess) { delete s; return nullptr; }      // nothing half-allocated stays behind: the call fails with NOMEM and may be retried
   c->slice_state = s;
   return s;
 }
@@ -2366,27 +2405,12 @@ static SliceState *slice_state(jmhip_ctx *c)
 static int ep_state_ensure(jmhip_ctx *c, SliceState *s, int search_range)
 {
   const int side = 2 * search_range + 1, cells = (side * side + 3) & ~3;
-  if (s->ep_cells == cells) return JMHIP_OK;
-  void *old[] = {s->ep_map, s->ep_map_next, s->ep_count, s->ep_count_next, s->ep_first, s->ep_last, s->ep_alias_flag, s->ep_nsearch, s->ep_base, s->ep_seg_last, s->ep_seg_in, s->ep_alias,
-                 s->ep_alias_new, s->ep_alias_n};
-  for (void *b : old) if (b) (void)hipFree(b);
-  s->ep_map = s->ep_map_next = nullptr; s->ep_count = s->ep_count_next = nullptr; s->ep_first = s->ep_last = s->ep_alias_flag = nullptr; s->ep_nsearch = nullptr;
-  s->ep_base = s->ep_seg_last = s->ep_seg_in = nullptr; s->ep_alias = s->ep_alias_new = nullptr; s->ep_alias_n = nullptr; s->ep_cells = 0;
-  const size_t nmb = (size_t)c->mbw * c->mbh, nseg = (nmb + EP_SEG - 1) / EP_SEG;
-  const bool ok = hipMalloc((void **)&s->ep_map, sizeof(uint16_t) * cells) == hipSuccess && hipMalloc((void **)&s->ep_map_next, sizeof(uint16_t) * cells) == hipSuccess &&
-                  hipMalloc((void **)&s->ep_count, sizeof(uint32_t)) == hipSuccess && hipMalloc((void **)&s->ep_count_next, sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc((void **)&s->ep_first, nmb * cells) == hipSuccess && hipMalloc((void **)&s->ep_last, nmb * cells) == hipSuccess &&
-                  hipMalloc((void **)&s->ep_alias_flag, nmb) == hipSuccess && hipMalloc((void **)&s->ep_nsearch, sizeof(uint16_t) * nmb) == hipSuccess &&
-                  hipMalloc((void **)&s->ep_base, sizeof(uint32_t) * (nmb + 1)) == hipSuccess && hipMalloc((void **)&s->ep_seg_last, sizeof(uint32_t) * nseg * cells) == hipSuccess &&
-                  hipMalloc((void **)&s->ep_seg_in, sizeof(uint32_t) * nseg * cells) == hipSuccess && hipMalloc((void **)&s->ep_alias, sizeof(unsigned long long) * EP_ALIAS_CAP) == hipSuccess &&
-                  hipMalloc((void **)&s->ep_alias_new, sizeof(unsigned long long) * EP_ALIAS_CAP) == hipSuccess && hipMalloc((void **)&s->ep_alias_n, sizeof(int)) == hipSuccess;
-  if (!ok) return jm_fail(c, JMHIP_ERR_NOMEM, "EPZS map state of the slice search");
-  s->ep_cells = cells;
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_map, 0, sizeof(uint16_t) * cells, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_count, 0, sizeof(uint32_t), c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_first, 0, nmb * cells, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_last, 0, nmb * cells, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_nsearch, 0, sizeof(uint16_t) * nmb, c->stream));
+  if (s->ep.cells == cells) return JMHIP_OK;
+  s->ep = EpMaps();                            // the old group goes first; a group that cannot be allocated in full is dropped
+  EpMaps ep;
+  if (!ep.alloc((size_t)c->mbw * c->mbh, cells)) return jm_fail(c, JMHIP_ERR_NOMEM, "EPZS map state of the slice search");
+  s->ep = std::move(ep);
+  for (const DevBuf *b : {&s->ep.map, &s->ep.count, &s->ep.first, &s->ep.last, &s->ep.nsearch}) JM_HIP_CHECK(c, fill(c, *b, 0));
   return JMHIP_OK;
 }
 
@@ -2396,19 +2420,11 @@ extern "C" int jmhip_slice_state_reset(jmhip_ctx *c)
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   SliceState *s = slice_state(c);
   if (!s) return jm_fail(c, JMHIP_ERR_NOMEM, "slice search state");
-  const size_t w4 = c->W / 4, h4 = c->H / 4;
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_dist, 0, sizeof(int) * (c->mbh + 1) * 7 * w4, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_motion, 0, sizeof(short) * (c->mbh + 1) * WR * 7 * 4 * w4 * 2, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->carry_mb, 0, sizeof(short) * (size_t)c->mbw * c->mbh * WR * CARRY * 2, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_col, 0, sizeof(short) * h4 * w4 * 2, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->carry_slice, 0, sizeof(short) * WR * CARRY * 2, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->carry_in, 0, sizeof(short) * c->mbh * WR * CARRY * 2, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->um_cost, 0, sizeof(int) * 8 * h4 * w4, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ref_idx, 0xff, w4 * h4, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(s->mv, 0, w4 * h4 * 4, c->stream));
+  for (const DevBuf *b : {&s->ep_dist, &s->ep_motion, &s->carry_mb, &s->ep_col, &s->carry_slice, &s->carry_in, &s->um_cost}) JM_HIP_CHECK(c, fill(c, *b, 0));
+  JM_HIP_CHECK(c, fill(c, s->ref_idx, 0xff));
+  JM_HIP_CHECK(c, fill(c, s->mv, 0));
   // EPZSMap is calloc'ed and EPZSBlkCount starts at zero (me_epzs.c:49,396)
-  if (s->ep_map) JM_HIP_CHECK(c, hipMemsetAsync(s->ep_map, 0, sizeof(uint16_t) * s->ep_cells, c->stream));
-  if (s->ep_count) JM_HIP_CHECK(c, hipMemsetAsync(s->ep_count, 0, sizeof(uint32_t), c->stream));
+  if (s->ep.cells) for (const DevBuf *b : {&s->ep.map, &s->ep.count}) JM_HIP_CHECK(c, fill(c, *b, 0));
   s->ep_aliases = 0;
   s->has_col = false;
   return JMHIP_OK;
@@ -2420,13 +2436,16 @@ extern "C" int jmhip_epzs_colocated_upload(jmhip_ctx *c, const int16_t *col_mv)
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   SliceState *s = slice_state(c);
   if (!s) return jm_fail(c, JMHIP_ERR_NOMEM, "slice search state");
-  JM_HIP_CHECK(c, hipMemcpyAsync(s->ep_col, col_mv, sizeof(short) * (size_t)(c->H / 4) * (c->W / 4) * 2, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(s->ep_col.ptr, col_mv, s->ep_col.bytes, hipMemcpyHostToDevice, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   s->has_col = true;
   return JMHIP_OK;
 }
 
-extern "C" int jmhip_p_slice_search(jmhip_ctx *c, const jmhip_slice_params *prm, jmhip_mb_inter *results)
+// ---------------------------------------------------------------------------------------------- the driver: jmhip_p_slice_search, step by step
+
+// what a call may ask for; no device call, no state touched
+static int check_slice_args(jmhip_ctx *c, const jmhip_slice_params *prm)
 {
   if (!c || !prm) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: NULL arguments") : JMHIP_ERR_ARG;
   const int nmb = c->mbw * c->mbh;
@@ -2460,233 +2479,293 @@ extern "C" int jmhip_p_slice_search(jmhip_ctx *c, const jmhip_slice_params *prm,
     if (sl < 0 || sl >= (int)c->refs.size() || !c->refs[sl].has_pic || !c->refs[sl].has_luma_sub) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: reference slot without sub-pel planes (jmhip_interp_luma)");
   }
   if (prm->search_mode == JMHIP_SEARCH_EPZS && (prm->epzs_nwin > 40 || prm->epzs_nwin_ext > 100 || prm->epzs_nwin < 0 || prm->epzs_nwin_ext < 0)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: EPZS window predictor tables (jmhip_epzs_setup)");
-  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  SliceState *s = slice_state(c);
-  if (!s) return jm_fail(c, JMHIP_ERR_NOMEM, "slice search state");
-  if (prm->search_mode == JMHIP_SEARCH_EPZS && prm->epzs_temporal && !s->has_col) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: EPZS temporal predictors need jmhip_epzs_colocated_upload");
-  int rc = jm_ensure_ref_table(c);
+  return JMHIP_OK;
+}
+
+static int env_int(const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; }
+
+static SliceKnobs read_knobs()
+{
+  SliceKnobs k;
+  const char *sched = getenv("JMHIP_SLICE_SCHED");
+  k.relax_grid = sched && !strcmp(sched, "wave") ? 0 : std::max(1, env_int("JMHIP_SLICE_GRID", 2048));
+  k.sweeps = env_int("JMHIP_SLICE_SWEEPS", 160);
+  k.memo = env_int("JMHIP_SLICE_MEMO", 1) != 0;
+  k.reduced0 = env_int("JMHIP_SLICE_REDUCED0", 1) != 0;
+  k.trace = getenv("JMHIP_SLICE_TRACE") != nullptr;
+  k.debug = env_int("JMHIP_WAVE_DEBUG", 0);
+  return k;
+}
+
+// search_mode -> its instantiation of the two slice kernels (the argument check admits these five)
+// (the tables name the instantiations in the order the device code has always been emitted in: the sweeps' five, then the walk's)
+struct SliceKernels { void (*relax)(const short *); void (*walk)(const short *, short *); };
+static SliceKernels slice_kernels(int search_mode)
+{
+  void (*const relax[5])(const short *) = {p_slice_relax_kernel<JMHIP_SEARCH_EPZS>, p_slice_relax_kernel<JMHIP_SEARCH_UMHEX>, p_slice_relax_kernel<JMHIP_SEARCH_UMHEX_SIMPLE>,
+                                           p_slice_relax_kernel<JMHIP_SEARCH_FASTFULL>, p_slice_relax_kernel<JMHIP_SEARCH_FULL>};
+  void (*const walk[5])(const short *, short *) = {p_slice_kernel<JMHIP_SEARCH_EPZS>, p_slice_kernel<JMHIP_SEARCH_UMHEX>, p_slice_kernel<JMHIP_SEARCH_UMHEX_SIMPLE>,
+                                                   p_slice_kernel<JMHIP_SEARCH_FASTFULL>, p_slice_kernel<JMHIP_SEARCH_FULL>};
+  const int k = search_mode == JMHIP_SEARCH_EPZS ? 0 : search_mode == JMHIP_SEARCH_UMHEX ? 1 : search_mode == JMHIP_SEARCH_UMHEX_SIMPLE ? 2 : search_mode == JMHIP_SEARCH_FASTFULL ? 3 : 4;
+  return {relax[k], walk[k]};
+}
+
+// the exhaustive searches go through the frame kernels' sweeps (me_xslice.hip) where those cover the configuration; what they do not cover,
+// or do not settle within their cap, runs on this file's one-wave-per-macroblock kernels
+int SliceCall::sweep_frame_kernels()
+{
+  int settled = 0, passes = 0;
+  s->passes = 0;
+  StageScope timed(c, JMHIP_STAGE_ME_INT);
+  const int rc = jm_xslice_run(c, prm, s->ref_idx.as<int8_t>(), s->mv.as<short>(), s->out.as<jmhip_mb_inter>(), &passes, &settled);
   if (rc) return rc;
-  const size_t w4 = c->W / 4, h4 = c->H / 4;
-  const int row_first = prm->mb_first / c->mbw, row_last = (prm->mb_first + prm->mb_count - 1) / c->mbw, rows = row_last - row_first + 1;
-  // (a new picture's enc_picture->ref_idx / mv need no reset: a macroblock only ever reads entries of macroblocks coded before it, and the
-  // previous picture's field is the relaxation schedule's first guess)
-  const bool exhaustive = prm->search_mode == JMHIP_SEARCH_FULL || prm->search_mode == JMHIP_SEARCH_FASTFULL;
-  // the slice's entries of the 8x8-transform pass's references: -1 unless a macroblock kernel of this call writes them (the sweeps over the frame
-  // kernels never run that pass); the other slices' entries stay
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ref8ts + (size_t)prm->mb_first * 4, 0xff, sizeof(int) * 4 * (size_t)prm->mb_count, c->stream));
-  // schedule: relaxation sweeps over `relax_grid` resident workgroups (default), or JMHIP_SLICE_SCHED=wave: the coding-order wavefront only
-  int relax_grid = 0;
-  {
-    const char *e = getenv("JMHIP_SLICE_SCHED");
-    if (!(e && !strcmp(e, "wave"))) relax_grid = 2048;                                      // two waves per SIMD (256 VGPRs): all that can be resident
-    if (const char *g = getenv("JMHIP_SLICE_GRID")) if (relax_grid) relax_grid = std::max(1, atoi(g));
-  }
-  // the exhaustive searches go through the frame kernels' sweeps (me_xslice.hip) where those cover the configuration; what they do not cover,
-  // or do not settle within their cap, runs on this file's one-wave-per-macroblock kernels
-  const bool x_path = exhaustive && relax_grid && jm_xslice_covers(prm);
-  bool x_settled = false;
-  if (x_path) {
-    int xs = 0, xp = 0;
-    s->passes = 0;
-    jm_stage_begin(c, JMHIP_STAGE_ME_INT);
-    rc = jm_xslice_run(c, prm, s->ref_idx, s->mv, s->out, &xp, &xs);
-    jm_stage_end(c, JMHIP_STAGE_ME_INT);
-    if (rc) return rc;
-    s->passes = xp;
-    x_settled = xs != 0;
-    if (!x_settled && prm->search_range > 33) return jm_fail(c, JMHIP_ERR_DEVICE, "jmhip_p_slice_search: the sweeps did not settle within their cap and the range exceeds what the macroblock kernels take over (33)");
-  }
-  if (exhaustive && !x_settled) {
-    const int rs = prm->search_range + SURF_MARGIN, n = ((2 * rs + 1) * (2 * rs + 1) + 63) & ~63;
-    const size_t slots = (size_t)std::max(rows, relax_grid);      // one surface set per resident workgroup (blockIdx.x)
-    if (s->surf_rows < slots || s->surf_n < n || s->surf_refs < prm->num_refs) {
-      if (s->surf) JM_HIP_CHECK(c, hipFree(s->surf));
-      s->surf = nullptr; s->surf_rows = 0;
-      if (hipMalloc((void **)&s->surf, sizeof(uint16_t) * slots * 2 * prm->num_refs * SURF_PLANES * n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "SAD surfaces of the slice search");
-      s->surf_rows = slots; s->surf_n = n; s->surf_refs = prm->num_refs;
-    }
-  }
-  WaveDev D{};
+  s->passes = passes;
+  x_settled = settled != 0;
+  if (!x_settled && prm->search_range > 33) return jm_fail(c, JMHIP_ERR_DEVICE, "jmhip_p_slice_search: the sweeps did not settle within their cap and the range exceeds what the macroblock kernels take over (33)");
+  return JMHIP_OK;
+}
+
+// SAD surfaces of the exhaustive searches: one set per resident workgroup (blockIdx.x), grown when a call needs more
+int SliceCall::ensure_surfaces()
+{
+  const int rs = prm->search_range + SURF_MARGIN, n = ((2 * rs + 1) * (2 * rs + 1) + 63) & ~63, refs = prm->num_refs;
+  const size_t slots = (size_t)std::max(rows, knobs.relax_grid);
+  if (s->surf_rows >= slots && s->surf_n >= n && s->surf_refs >= refs) return JMHIP_OK;
+  s->surf_rows = 0;
+  if (!s->surf.alloc(sizeof(uint16_t) * slots * 2 * refs * SURF_PLANES * n)) return jm_fail(c, JMHIP_ERR_NOMEM, "SAD surfaces of the slice search");
+  s->surf_rows = slots; s->surf_n = n; s->surf_refs = refs;
+  return JMHIP_OK;
+}
+
+// exhaustive searches: the spiral index + 1 of every offset of the search window (WaveDev.tie_tab), rebuilt when the range changes
+int SliceCall::ensure_tie_table()
+{
+  const int R = prm->search_range, side = 2 * R + 1;
+  if (s->tie_R == R) return JMHIP_OK;
+  std::vector<uint16_t> t((size_t)side * side);
+  for (int dy = -R; dy <= R; dy++) for (int dx = -R; dx <= R; dx++) t[(size_t)(dy + R) * side + (dx + R)] = (uint16_t)(spiral_pos(dx, dy) + 1);
+  s->tie_R = 0;
+  if (!s->tie_tab.alloc(t.size() * sizeof(uint16_t))) return jm_fail(c, JMHIP_ERR_NOMEM, "spiral table of the slice search");
+  JM_HIP_CHECK(c, hipMemcpyAsync(s->tie_tab.ptr, t.data(), s->tie_tab.bytes, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  s->tie_R = R;
+  return JMHIP_OK;
+}
+
+// the kernels' parameter block (c_wave), but for what changes from sweep to sweep and the EPZS map state (prepare_epzs)
+void SliceCall::fill_wave_dev()
+{
   D.p = *prm;
-  D.surf = s->surf; D.surf_n = s->surf_n;
-  D.debug = getenv("JMHIP_WAVE_DEBUG") ? atoi(getenv("JMHIP_WAVE_DEBUG")) : 0;
+  D.surf = s->surf.as<uint16_t>(); D.surf_n = s->surf_n;
+  D.debug = knobs.debug;
   if (D.debug) fprintf(stderr, "jmhip: JMHIP_WAVE_DEBUG=%d is set: stages of the slice search are SKIPPED for timing experiments, its results are WRONG\n", D.debug);
-  D.W = c->W; D.H = c->H; D.Wp = c->Wp; D.Hp = c->Hp; D.mbw = c->mbw; D.mbh = c->mbh; D.w4 = (int)w4; D.h4 = (int)h4;
+  D.W = c->W; D.H = c->H; D.Wp = c->Wp; D.Hp = c->Hp; D.mbw = c->mbw; D.mbh = c->mbh; D.w4 = c->W / 4; D.h4 = c->H / 4;
   D.cur = c->cur_y;
   D.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
-  D.ref_idx = s->ref_idx; D.mv = s->mv; D.prog = s->prog; D.flags = s->flags; D.out = s->out; D.ref8ts = s->ref8ts;
-  D.ep_dist = s->ep_dist; D.ep_motion = s->ep_motion; D.ep_col = s->ep_col; D.row0 = row_first;
-  D.carry_in = s->carry_in; D.carry_out = s->carry_out; D.um_cost = s->um_cost; D.um_in = s->um_cost_snap; D.carry_mb = s->carry_mb;
-  D.n_changed = s->flags + 2;
-  D.memo = s->memo;
-  if (exhaustive) {
-    if (s->tie_R != prm->search_range) {
-      const int R = prm->search_range, side = 2 * R + 1;
-      std::vector<uint16_t> t((size_t)side * side);
-      for (int dy = -R; dy <= R; dy++) for (int dx = -R; dx <= R; dx++) {        // spiral_search_x / _y order, mv-search.c:366-393 (me_common.h spiral_pos)
-        const int adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy, l = std::max(adx, ady);
-        int pos = 0;
-        if (l) {
-          const int k0 = (2 * l - 1) * (2 * l - 1);
-          pos = (ady == l && adx < l) ? k0 + 2 * (dx + l - 1) + (dy > 0 ? 1 : 0) : k0 + 2 * (2 * l - 1) + 2 * (dy + l) + (dx > 0 ? 1 : 0);
-        }
-        t[(size_t)(dy + R) * side + (dx + R)] = (uint16_t)(pos + 1);
-      }
-      if (s->tie_tab) JM_HIP_CHECK(c, hipFree(s->tie_tab));
-      s->tie_tab = nullptr; s->tie_R = 0;
-      if (hipMalloc((void **)&s->tie_tab, t.size() * sizeof(uint16_t)) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "spiral table of the slice search");
-      JM_HIP_CHECK(c, hipMemcpyAsync(s->tie_tab, t.data(), t.size() * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-      JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      s->tie_R = R;
-    }
-    D.tie_tab = s->tie_tab; D.tie_R = s->tie_R;
-  }
-  D.memo_on = exhaustive && relax_grid && !prm->transform8x8_mode && !(getenv("JMHIP_SLICE_MEMO") && !atoi(getenv("JMHIP_SLICE_MEMO")));
-  const bool epzs = prm->search_mode == JMHIP_SEARCH_EPZS;
-  std::vector<unsigned long long> ep_used;       // EPZS: the map tests this call's searches took as answered from an old stamp (sorted)
-  // a macroblock's own cost-map entries start from what the slice found (mb_stage)
-  if (prm->search_mode == JMHIP_SEARCH_UMHEX) JM_HIP_CHECK(c, hipMemcpyAsync(s->um_cost_snap, s->um_cost, sizeof(int) * 8 * h4 * w4, hipMemcpyDeviceToDevice, c->stream));
-  if (!x_path) s->passes = 0;
-  if (epzs) {
-    rc = ep_state_ensure(c, s, prm->search_range);
-    if (rc) return rc;
-    if (45 * prm->num_refs >= EP_STAMPED) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_p_slice_search: EPZS search counts per macroblock are kept in 8 bits");
-    JM_HIP_CHECK(c, hipMemsetAsync(s->ep_alias_flag, 0, (size_t)nmb, c->stream));
-    D.ep_first = s->ep_first; D.ep_last = s->ep_last; D.ep_nsearch = s->ep_nsearch; D.ep_cells = s->ep_cells;
-    D.ep_alias = s->ep_alias; D.ep_alias_n = 0; D.ep_alias_flag = s->ep_alias_flag;
-    s->ep_aliases = 0;
-  }
-  jm_stage_begin(c, JMHIP_STAGE_ME_INT);
-  bool settled = x_settled;
-  int sweep_no = 0;                              // sweeps of this call so far (the changed-flag arrays alternate with it)
-  // the walkers' sweep 0 searches the 16x16 mode only (JMHIP_SLICE_REDUCED0=0: a full sweep 0). Measured per new 1080p picture, bench clip: EPZS 32 / 23 / 55 -> 24 / 23 / 47 ms,
-  // UMHexagonS 19.5 / 19.5 / 38 -> 16 / 16.5 / 36 ms; the smooth clip within +-5 %
-  const bool reduced0 = !exhaustive && !(getenv("JMHIP_SLICE_REDUCED0") && !atoi(getenv("JMHIP_SLICE_REDUCED0")));
-  // the slice under the current set of pre-marked map cells: relaxation sweeps to the fixpoint, else the coding-order walk
-  auto settle = [&]() -> int {
-  if (relax_grid && !settled) {
-    // relaxation sweeps (p_slice_relax_kernel); the coding-order walk below remains the fallback if they do not settle within the cap
-    const int cap = getenv("JMHIP_SLICE_SWEEPS") ? atoi(getenv("JMHIP_SLICE_SWEEPS")) : 160;      // a sweep costs >= one macroblock (1.2 ms), the walk 250+
-    const int grid = std::min(relax_grid, prm->mb_count);
-    for (int sweep = 0; sweep < cap && !settled; sweep++, sweep_no++) {
-      JM_HIP_CHECK(c, hipMemsetAsync(s->flags, 0, sizeof(int) * 4, c->stream));
-      // sweep 0 searches the 16x16 mode only -- a first guess of the field at a fraction of a full sweep's cost (any start reaches the same fixpoint) --
-      // and sweep 1 evaluates every macroblock in full whatever changed
-      D.reduced = reduced0 && sweep_no == 0;
-      D.first_sweep = sweep_no == 0 || (reduced0 && sweep_no == 1); D.chg_prev = s->chg[sweep_no & 1]; D.chg_next = s->chg[(sweep_no + 1) & 1];
-      JM_HIP_CHECK(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_wave), &D, sizeof(D), 0, hipMemcpyHostToDevice, c->stream));
-      switch (prm->search_mode) {
-      case JMHIP_SEARCH_EPZS: p_slice_relax_kernel<JMHIP_SEARCH_EPZS><<<grid, 64, 0, c->stream>>>(s->carry_slice); break;
-      case JMHIP_SEARCH_UMHEX: p_slice_relax_kernel<JMHIP_SEARCH_UMHEX><<<grid, 64, 0, c->stream>>>(s->carry_slice); break;
-      case JMHIP_SEARCH_UMHEX_SIMPLE: p_slice_relax_kernel<JMHIP_SEARCH_UMHEX_SIMPLE><<<grid, 64, 0, c->stream>>>(s->carry_slice); break;
-      case JMHIP_SEARCH_FASTFULL: p_slice_relax_kernel<JMHIP_SEARCH_FASTFULL><<<grid, 64, 0, c->stream>>>(s->carry_slice); break;
-      default: p_slice_relax_kernel<JMHIP_SEARCH_FULL><<<grid, 64, 0, c->stream>>>(s->carry_slice); break;
-      }
-      JM_HIP_CHECK(c, hipGetLastError());
-      s->passes++;
-      int flags[4] = {0, 0, 1, 0};
-      JM_HIP_CHECK(c, hipMemcpyAsync(flags, s->flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-      JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      settled = flags[2] == 0;
-      if (getenv("JMHIP_SLICE_TRACE")) {
-        static double t_last = 0.0;
-        struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
-        const double t_now = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-        fprintf(stderr, "sweep %d: %d macroblocks changed what they hand on (%.2f ms since the previous line)\n", sweep_no, flags[2], t_now - t_last);
-        t_last = t_now;
-      }
-    }
-    if (settled && !x_settled)
-      JM_HIP_CHECK(c, hipMemcpyAsync(s->carry_slice_next, s->carry_mb + (size_t)(prm->mb_first + prm->mb_count - 1) * WR * CARRY * 2, sizeof(short) * WR * CARRY * 2, hipMemcpyDeviceToDevice, c->stream));
-  }
-  for (; !settled;) {
-    D.reduced = 0;                                 // the coding-order walk evaluates every macroblock once, in full
-    JM_HIP_CHECK(c, hipMemsetAsync(s->prog, 0, sizeof(int) * c->mbh, c->stream));
-    const int init_flags[4] = {0, 1 << 30, 0, 0};
-    JM_HIP_CHECK(c, hipMemcpyAsync(s->flags, init_flags, sizeof(init_flags), hipMemcpyHostToDevice, c->stream));
+  D.ref_idx = s->ref_idx.as<int8_t>(); D.mv = s->mv.as<short>(); D.prog = s->prog.as<int>(); D.flags = s->flags.as<int>();
+  D.out = s->out.as<jmhip_mb_inter>(); D.ref8ts = s->ref8ts.as<int>();
+  D.ep_dist = s->ep_dist.as<int>(); D.ep_motion = s->ep_motion.as<short>(); D.ep_col = s->ep_col.as<short>(); D.row0 = row_first;
+  D.carry_in = s->carry_in.as<short>(); D.carry_out = s->carry_out.as<short>(); D.carry_mb = s->carry_mb.as<short>();
+  D.um_cost = s->um_cost.as<int>(); D.um_in = s->um_cost_snap.as<int>();
+  D.n_changed = D.flags + 2;
+  D.memo = s->memo.as<unsigned long long>();
+  D.memo_on = exhaustive && knobs.relax_grid && !prm->transform8x8_mode && knobs.memo;
+  if (exhaustive) { D.tie_tab = s->tie_tab.as<uint16_t>(); D.tie_R = s->tie_R; }
+}
+
+// EPZS: the map state of this search range, no macroblock marked for another search, no test pre-marked yet
+int SliceCall::prepare_epzs()
+{
+  const int rc = ep_state_ensure(c, s, prm->search_range);
+  if (rc) return rc;
+  if (45 * prm->num_refs >= EP_STAMPED) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_p_slice_search: EPZS search counts per macroblock are kept in 8 bits");
+  JM_HIP_CHECK(c, fill(c, s->ep.alias_flag, 0));
+  D.ep_first = s->ep.first.as<uint8_t>(); D.ep_last = s->ep.last.as<uint8_t>(); D.ep_nsearch = s->ep.nsearch.as<uint16_t>(); D.ep_cells = s->ep.cells;
+  D.ep_alias = s->ep.alias.as<unsigned long long>(); D.ep_alias_n = 0; D.ep_alias_flag = s->ep.alias_flag.as<uint8_t>();
+  s->ep_aliases = 0;
+  return JMHIP_OK;
+}
+
+// relaxation sweeps (p_slice_relax_kernel) until no macroblock changes what it hands on, or the cap; the coding-order walk remains the fallback
+// if they do not settle
+int SliceCall::relax_to_fixpoint()
+{
+  const bool reduced0 = !exhaustive && knobs.reduced0;
+  const int grid = std::min(knobs.relax_grid, prm->mb_count);
+  for (int sweep = 0; sweep < knobs.sweeps && !settled; sweep++, sweep_no++) {
+    JM_HIP_CHECK(c, fill(c, s->flags, 0));
+    // sweep 0 searches the 16x16 mode only -- a first guess of the field at a fraction of a full sweep's cost (any start reaches the same fixpoint) --
+    // and sweep 1 evaluates every macroblock in full whatever changed
+    D.reduced = reduced0 && sweep_no == 0;
+    D.first_sweep = sweep_no == 0 || (reduced0 && sweep_no == 1);
+    D.chg_prev = s->chg[sweep_no & 1].as<uint8_t>(); D.chg_next = s->chg[(sweep_no + 1) & 1].as<uint8_t>();
     JM_HIP_CHECK(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_wave), &D, sizeof(D), 0, hipMemcpyHostToDevice, c->stream));
-    switch (prm->search_mode) {
-    case JMHIP_SEARCH_EPZS: p_slice_kernel<JMHIP_SEARCH_EPZS><<<rows, 64, 0, c->stream>>>(s->carry_slice, s->carry_slice_next); break;
-    case JMHIP_SEARCH_UMHEX: p_slice_kernel<JMHIP_SEARCH_UMHEX><<<rows, 64, 0, c->stream>>>(s->carry_slice, s->carry_slice_next); break;
-    case JMHIP_SEARCH_UMHEX_SIMPLE: p_slice_kernel<JMHIP_SEARCH_UMHEX_SIMPLE><<<rows, 64, 0, c->stream>>>(s->carry_slice, s->carry_slice_next); break;
-    case JMHIP_SEARCH_FASTFULL: p_slice_kernel<JMHIP_SEARCH_FASTFULL><<<rows, 64, 0, c->stream>>>(s->carry_slice, s->carry_slice_next); break;
-    default: p_slice_kernel<JMHIP_SEARCH_FULL><<<rows, 64, 0, c->stream>>>(s->carry_slice, s->carry_slice_next); break;
+    slice_kernels(prm->search_mode).relax<<<grid, 64, 0, c->stream>>>(s->carry_slice.as<short>());
+    JM_HIP_CHECK(c, hipGetLastError());
+    s->passes++;
+    int flags[4] = {0, 0, 1, 0};
+    JM_HIP_CHECK(c, hipMemcpyAsync(flags, s->flags.ptr, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    settled = flags[2] == 0;
+    if (knobs.trace) {
+      static double t_last = 0.0;
+      struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
+      const double t_now = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+      fprintf(stderr, "sweep %d: %d macroblocks changed what they hand on (%.2f ms since the previous line)\n", sweep_no, flags[2], t_now - t_last);
+      t_last = t_now;
     }
+  }
+  if (settled && !x_settled)
+    JM_HIP_CHECK(c, hipMemcpyAsync(s->carry_slice_next.ptr, s->carry_mb.as<short>() + (size_t)(prm->mb_first + prm->mb_count - 1) * WR * CARRY * 2, s->carry_slice_next.bytes, hipMemcpyDeviceToDevice, c->stream));
+  return JMHIP_OK;
+}
+
+// the coding-order walk (p_slice_kernel): one wave per macroblock row, every macroblock once and in full; EPZS repeats it until every row started
+// from what the row above left
+int SliceCall::walk_coding_order()
+{
+  const size_t row_carry = (size_t)WR * CARRY * 2;
+  D.reduced = 0;
+  for (;;) {
+    JM_HIP_CHECK(c, fill(c, s->prog, 0));
+    const int init_flags[4] = {0, 1 << 30, 0, 0};
+    JM_HIP_CHECK(c, hipMemcpyAsync(s->flags.ptr, init_flags, sizeof(init_flags), hipMemcpyHostToDevice, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_wave), &D, sizeof(D), 0, hipMemcpyHostToDevice, c->stream));
+    slice_kernels(prm->search_mode).walk<<<rows, 64, 0, c->stream>>>(s->carry_slice.as<short>(), s->carry_slice_next.as<short>());
     JM_HIP_CHECK(c, hipGetLastError());
     s->passes++;
     int flags[4] = {0, 1 << 30, 0, 0};
-    if (epzs && rows > 1) carry_check_kernel<<<(rows + 63) / 64, 64, 0, c->stream>>>(s->carry_in, s->carry_out, row_first, rows, s->flags);
-    JM_HIP_CHECK(c, hipMemcpyAsync(flags, s->flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    if (epzs && rows > 1) carry_check_kernel<<<(rows + 63) / 64, 64, 0, c->stream>>>(s->carry_in.as<short>(), s->carry_out.as<short>(), row_first, rows, s->flags.as<int>());
+    JM_HIP_CHECK(c, hipMemcpyAsync(flags, s->flags.ptr, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
     JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (flags[0]) { return jm_fail(c, JMHIP_ERR_DEVICE, "p_slice_kernel: a row waited too long for the row above (internal error)"); }
-    if (!epzs || rows == 1 || flags[1] == (1 << 30)) break;
-    if (s->passes > rows + 80) { return jm_fail(c, JMHIP_ERR_DEVICE, "p_slice_kernel: row-start speculation did not settle (internal error)"); }
+    if (flags[0]) return jm_fail(c, JMHIP_ERR_DEVICE, "p_slice_kernel: a row waited too long for the row above (internal error)");
+    if (!epzs || rows == 1 || flags[1] == (1 << 30)) return JMHIP_OK;
+    if (s->passes > rows + 80) return jm_fail(c, JMHIP_ERR_DEVICE, "p_slice_kernel: row-start speculation did not settle (internal error)");
     // next pass: every row starts from what the row above left in this pass; rows up to the first wrong one were exact already. (The stored
     // rows of the row memories are rewritten in coding order by every pass; row 0, what the slice found, is never written.)
-    JM_HIP_CHECK(c, hipMemcpyAsync(s->carry_in + (size_t)(row_first + 1) * WR * CARRY * 2, s->carry_out + (size_t)row_first * WR * CARRY * 2,
-                                   sizeof(short) * (size_t)(rows - 1) * WR * CARRY * 2, hipMemcpyDeviceToDevice, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyAsync(s->carry_in.as<short>() + (row_first + 1) * row_carry, s->carry_out.as<short>() + row_first * row_carry, sizeof(short) * (rows - 1) * row_carry,
+                                   hipMemcpyDeviceToDevice, c->stream));
   }
+}
+
+// JM's map across the slice's searches: which tests would an old stamp have answered? (ep_alias_* kernels) *again: the answer differs from what
+// this round's searches were shown; the macroblocks concerned are marked and the slice has to settle once more
+int SliceCall::epzs_alias_round(int round, bool *again)
+{
+  EpMaps &ep = s->ep;
+  const int nmb = c->mbw * c->mbh, cells = ep.cells, nseg = (prm->mb_count + EP_SEG - 1) / EP_SEG;
+  *again = false;
+  JM_HIP_CHECK(c, fill(c, ep.alias_n, 0));
+  ep_alias_base_kernel<<<1, 1024, 0, c->stream>>>(ep.nsearch.as<uint16_t>(), prm->mb_first, prm->mb_count, ep.count.as<uint32_t>(), ep.base.as<uint32_t>(), ep.count_next.as<uint32_t>());
+  ep_alias_seglast_kernel<<<dim3((cells + 255) / 256, nseg), 256, 0, c->stream>>>(ep.last.as<uint8_t>(), ep.base.as<uint32_t>(), prm->mb_first, prm->mb_count, cells, ep.seg_last.as<uint32_t>());
+  ep_alias_segin_kernel<<<(cells + 255) / 256, 256, 0, c->stream>>>(ep.seg_last.as<uint32_t>(), nseg, cells, ep.map.as<uint16_t>(), ep.seg_in.as<uint32_t>(), ep.map_next.as<uint16_t>());
+  ep_alias_detect_kernel<<<dim3((cells + 255) / 256, nseg), 256, 0, c->stream>>>(ep.first.as<uint8_t>(), ep.last.as<uint8_t>(), ep.nsearch.as<uint16_t>(), ep.base.as<uint32_t>(), ep.seg_in.as<uint32_t>(),
+                                                                               prm->mb_first, prm->mb_count, cells, ep.alias_new.as<unsigned long long>(), ep.alias_n.as<int>());
+  JM_HIP_CHECK(c, hipGetLastError());
+  int n_new = 0;
+  JM_HIP_CHECK(c, hipMemcpyAsync(&n_new, ep.alias_n.ptr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  if (n_new > EP_ALIAS_CAP) return jm_fail(c, JMHIP_ERR_DEVICE, "jmhip_p_slice_search: more aliased EPZS map tests in one slice than the list holds");
+  std::vector<unsigned long long> fresh((size_t)n_new);
+  if (n_new) {
+    JM_HIP_CHECK(c, hipMemcpyAsync(fresh.data(), ep.alias_new.ptr, sizeof(unsigned long long) * n_new, hipMemcpyDeviceToHost, c->stream));
+    JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    std::sort(fresh.begin(), fresh.end());
+  }
+  if (knobs.trace) fprintf(stderr, "EPZS map round %d: %d tests answered from an old stamp (%zu pre-marked in this round's searches)\n", round, n_new, ep_used.size());
+  if (fresh == ep_used) return JMHIP_OK;       // the searches ran with exactly the cells JM's map would have shown them
+  if (round >= 64) return jm_fail(c, JMHIP_ERR_DEVICE, "jmhip_p_slice_search: the aliased EPZS map tests did not settle (internal error)");
+  // search the macroblocks whose pre-marked cells changed again (they, and whatever their results change downstream, through the sweeps)
+  std::vector<uint8_t> fl((size_t)nmb, 0);
+  for (unsigned long long e : ep_used) fl[(size_t)(e >> 32)] |= 2;
+  for (unsigned long long e : fresh) fl[(size_t)(e >> 32)] |= 3;
+  ep_used.swap(fresh);
+  JM_HIP_CHECK(c, hipMemcpyAsync(ep.alias_flag.ptr, fl.data(), (size_t)nmb, hipMemcpyHostToDevice, c->stream));
+  if (!ep_used.empty()) JM_HIP_CHECK(c, hipMemcpyAsync(ep.alias.ptr, ep_used.data(), sizeof(unsigned long long) * ep_used.size(), hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  D.ep_alias_n = (int)ep_used.size();
+  settled = false;
+  *again = true;
   return JMHIP_OK;
-  };
+}
+
+// what this file's kernels have to do, as one me_int stage: the slice to its fixpoint (the sweeps, else the walk), for EPZS once per round of
+// pre-marked map cells until a round changes none; then EPZS's map, counter and row memories move on to what the slice left
+int SliceCall::search_slice()
+{
+  StageScope timed(c, JMHIP_STAGE_ME_INT);
+  settled = x_settled;
   for (int round = 0;; round++) {
-    rc = settle();
-    if (rc) { jm_stage_end(c, JMHIP_STAGE_ME_INT); return rc; }
-    if (!epzs) break;
-    // JM's map across the slice's searches: which tests would an old stamp have answered? (ep_alias_* kernels)
-    const int cells = s->ep_cells, nseg = (prm->mb_count + EP_SEG - 1) / EP_SEG;
-    JM_HIP_CHECK(c, hipMemsetAsync(s->ep_alias_n, 0, sizeof(int), c->stream));
-    ep_alias_base_kernel<<<1, 1024, 0, c->stream>>>(s->ep_nsearch, prm->mb_first, prm->mb_count, s->ep_count, s->ep_base, s->ep_count_next);
-    ep_alias_seglast_kernel<<<dim3((cells + 255) / 256, nseg), 256, 0, c->stream>>>(s->ep_last, s->ep_base, prm->mb_first, prm->mb_count, cells, s->ep_seg_last);
-    ep_alias_segin_kernel<<<(cells + 255) / 256, 256, 0, c->stream>>>(s->ep_seg_last, nseg, cells, s->ep_map, s->ep_seg_in, s->ep_map_next);
-    ep_alias_detect_kernel<<<dim3((cells + 255) / 256, nseg), 256, 0, c->stream>>>(s->ep_first, s->ep_last, s->ep_nsearch, s->ep_base, s->ep_seg_in, prm->mb_first, prm->mb_count, cells,
-                                                                                 s->ep_alias_new, s->ep_alias_n);
-    JM_HIP_CHECK(c, hipGetLastError());
-    int n_new = 0;
-    JM_HIP_CHECK(c, hipMemcpyAsync(&n_new, s->ep_alias_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (n_new > EP_ALIAS_CAP) { jm_stage_end(c, JMHIP_STAGE_ME_INT); return jm_fail(c, JMHIP_ERR_DEVICE, "jmhip_p_slice_search: more aliased EPZS map tests in one slice than the list holds"); }
-    std::vector<unsigned long long> fresh((size_t)n_new);
-    if (n_new) {
-      JM_HIP_CHECK(c, hipMemcpyAsync(fresh.data(), s->ep_alias_new, sizeof(unsigned long long) * n_new, hipMemcpyDeviceToHost, c->stream));
-      JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      std::sort(fresh.begin(), fresh.end());
-    }
-    if (getenv("JMHIP_SLICE_TRACE")) fprintf(stderr, "EPZS map round %d: %d tests answered from an old stamp (%zu pre-marked in this round's searches)\n", round, n_new, ep_used.size());
-    if (fresh == ep_used) break;                  // the searches ran with exactly the cells JM's map would have shown them
-    if (round >= 64) { jm_stage_end(c, JMHIP_STAGE_ME_INT); return jm_fail(c, JMHIP_ERR_DEVICE, "jmhip_p_slice_search: the aliased EPZS map tests did not settle (internal error)"); }
-    // search the macroblocks whose pre-marked cells changed again (they, and whatever their results change downstream, through the sweeps)
-    std::vector<uint8_t> fl((size_t)nmb, 0);
-    for (unsigned long long e : ep_used) fl[(size_t)(e >> 32)] |= 2;
-    for (unsigned long long e : fresh) fl[(size_t)(e >> 32)] |= 3;
-    ep_used.swap(fresh);
-    JM_HIP_CHECK(c, hipMemcpyAsync(s->ep_alias_flag, fl.data(), (size_t)nmb, hipMemcpyHostToDevice, c->stream));
-    if (!ep_used.empty()) JM_HIP_CHECK(c, hipMemcpyAsync(s->ep_alias, ep_used.data(), sizeof(unsigned long long) * ep_used.size(), hipMemcpyHostToDevice, c->stream));
-    JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    D.ep_alias_n = (int)ep_used.size();
-    settled = false;
+    int rc = knobs.relax_grid && !settled ? relax_to_fixpoint() : JMHIP_OK;
+    if (!rc && !settled) rc = walk_coding_order();
+    if (rc) return rc;
+    if (!epzs) return JMHIP_OK;
+    bool again = false;
+    if ((rc = epzs_alias_round(round, &again))) return rc;
+    if (!again) break;
   }
-  if (epzs) { std::swap(s->ep_map, s->ep_map_next); std::swap(s->ep_count, s->ep_count_next); s->ep_aliases = (int)ep_used.size(); }
-  if (epzs) epzs_rows_fold_kernel<<<((int)w4 + 63) / 64, 64, 0, c->stream>>>(s->ep_dist, s->ep_motion, (int)w4, c->mbw, prm->mb_first, prm->mb_count, row_first, prm->epzs_spatial_mem);
-  jm_stage_end(c, JMHIP_STAGE_ME_INT);
+  s->ep.map.swap(s->ep.map_next); s->ep.count.swap(s->ep.count_next); s->ep_aliases = (int)ep_used.size();
+  epzs_rows_fold_kernel<<<(c->W / 4 + 63) / 64, 64, 0, c->stream>>>(s->ep_dist.as<int>(), s->ep_motion.as<short>(), c->W / 4, c->mbw, prm->mb_first, prm->mb_count, row_first, prm->epzs_spatial_mem);
+  return JMHIP_OK;
+}
+
+static void report_wave_prof(jmhip_ctx *c)
+{
 #ifdef JMHIP_WAVE_PROF
-  {
-    unsigned long long h[16];
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wave_prof), sizeof(h));
-    const double nmb = h[9] ? (double)h[9] : 1.0;
-    fprintf(stderr, "WAVE PROF stage %.0f decide %.0f commit %.0f | ", h[13] / nmb, h[14] / nmb, h[15] / nmb);
-    fprintf(stderr, "WAVE PROF cycles per macroblock (%.0f MBs): total %.0f | predictor %.0f integer %.0f subpel %.0f skip %.0f | epzs: lists %.0f scan+eval %.0f refine %.0f | eval_dist: %.0f cycles in %.1f calls, %.1f candidates\n", nmb, h[8] / nmb,
-            h[0] / nmb, h[1] / nmb, h[2] / nmb, h[3] / nmb, h[4] / nmb, h[5] / nmb, h[6] / nmb, h[10] / nmb, h[11] / nmb, h[12] / nmb);
-    unsigned long long z[16] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wave_prof), z, sizeof(z));
-  }
+  unsigned long long h[16];
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wave_prof), sizeof(h));
+  const double nmb = h[9] ? (double)h[9] : 1.0;
+  fprintf(stderr, "WAVE PROF stage %.0f decide %.0f commit %.0f | ", h[13] / nmb, h[14] / nmb, h[15] / nmb);
+  fprintf(stderr, "WAVE PROF cycles per macroblock (%.0f MBs): total %.0f | predictor %.0f integer %.0f subpel %.0f skip %.0f | epzs: lists %.0f scan+eval %.0f refine %.0f | eval_dist: %.0f cycles in %.1f calls, %.1f candidates\n", nmb, h[8] / nmb,
+          h[0] / nmb, h[1] / nmb, h[2] / nmb, h[3] / nmb, h[4] / nmb, h[5] / nmb, h[6] / nmb, h[10] / nmb, h[11] / nmb, h[12] / nmb);
+  unsigned long long z[16] = {0};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wave_prof), z, sizeof(z));
 #endif
-  if (!x_settled) std::swap(s->carry_slice, s->carry_slice_next);      // (the exhaustive searches neither read nor write img->all_mv's carry)
+}
+
+// which macroblocks of the current picture have been searched, and how (the hand-over to the frame stage asks)
+static void note_searched(SliceState *s, const jmhip_slice_params *prm)
+{
   if (prm->mb_first == 0) s->t8_any = false;
   s->t8_any = s->t8_any || prm->transform8x8_mode != 0;
   // slices in coding order extend the searched range; anything else starts a new one (a rank of the slice-parallel layout searches only its band)
   if (prm->mb_first != 0 && prm->mb_first == s->searched_to) { s->searched_to = prm->mb_first + prm->mb_count; s->t8_all = s->t8_all && prm->transform8x8_mode != 0; }
   else { s->searched_from = prm->mb_first; s->searched_to = prm->mb_first + prm->mb_count; s->t8_all = prm->transform8x8_mode != 0; }
+}
+
+extern "C" int jmhip_p_slice_search(jmhip_ctx *c, const jmhip_slice_params *prm, jmhip_mb_inter *results)
+{
+  int rc = check_slice_args(c, prm);
+  if (rc) return rc;
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  SliceState *s = slice_state(c);
+  if (!s) return jm_fail(c, JMHIP_ERR_NOMEM, "slice search state");
+  if (prm->search_mode == JMHIP_SEARCH_EPZS && prm->epzs_temporal && !s->has_col) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: EPZS temporal predictors need jmhip_epzs_colocated_upload");
+  if ((rc = jm_ensure_ref_table(c))) return rc;
+  SliceCall q{c, prm, s, read_knobs()};
+  q.row_first = prm->mb_first / c->mbw;
+  q.rows = (prm->mb_first + prm->mb_count - 1) / c->mbw - q.row_first + 1;
+  q.exhaustive = prm->search_mode == JMHIP_SEARCH_FULL || prm->search_mode == JMHIP_SEARCH_FASTFULL;
+  q.epzs = prm->search_mode == JMHIP_SEARCH_EPZS;
+  // (a new picture's enc_picture->ref_idx / mv need no reset: a macroblock only ever reads entries of macroblocks coded before it, and the
+  // previous picture's field is the relaxation schedule's first guess)
+  // the slice's entries of the 8x8-transform pass's references: -1 unless a macroblock kernel of this call writes them (the sweeps over the frame
+  // kernels never run that pass); the other slices' entries stay
+  JM_HIP_CHECK(c, hipMemsetAsync(s->ref8ts.as<int>() + (size_t)prm->mb_first * 4, 0xff, sizeof(int) * 4 * (size_t)prm->mb_count, c->stream));
+  const bool x_path = q.exhaustive && q.knobs.relax_grid && jm_xslice_covers(prm);
+  if (x_path && (rc = q.sweep_frame_kernels())) return rc;
+  if (q.exhaustive && !q.x_settled && (rc = q.ensure_surfaces())) return rc;
+  if (q.exhaustive && (rc = q.ensure_tie_table())) return rc;
+  q.fill_wave_dev();
+  // a macroblock's own cost-map entries start from what the slice found (mb_stage)
+  if (prm->search_mode == JMHIP_SEARCH_UMHEX) JM_HIP_CHECK(c, hipMemcpyAsync(s->um_cost_snap.ptr, s->um_cost.ptr, s->um_cost.bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (!x_path) s->passes = 0;
+  if (q.epzs && (rc = q.prepare_epzs())) return rc;
+  if ((rc = q.search_slice())) return rc;
+  report_wave_prof(c);
+  if (!q.x_settled) s->carry_slice.swap(s->carry_slice_next);      // (the exhaustive searches neither read nor write img->all_mv's carry)
+  note_searched(s, prm);
   if (results) return jmhip_slice_results_download(c, results, prm->mb_first, prm->mb_count);
   return JMHIP_OK;
 }
@@ -2695,7 +2774,7 @@ extern "C" int jmhip_slice_results_download(jmhip_ctx *c, jmhip_mb_inter *result
 {
   if (!c || !results || mb_first < 0 || mb_count < 1 || mb_first + mb_count > c->mbw * c->mbh || !c->slice_state) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_results_download: arguments") : JMHIP_ERR_ARG;
   SliceState *s = static_cast<SliceState *>(c->slice_state);
-  JM_HIP_CHECK(c, hipMemcpyAsync(results, s->out + mb_first, sizeof(jmhip_mb_inter) * (size_t)mb_count, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(results, s->out.as<jmhip_mb_inter>() + mb_first, sizeof(jmhip_mb_inter) * (size_t)mb_count, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -2705,8 +2784,8 @@ extern "C" int jmhip_slice_field_download(jmhip_ctx *c, int8_t *ref_idx, int16_t
   if (!c || !c->slice_state) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_field_download: no slice has been searched") : JMHIP_ERR_ARG;
   SliceState *s = static_cast<SliceState *>(c->slice_state);
   const size_t n = (size_t)(c->W / 4) * (c->H / 4);
-  if (ref_idx) JM_HIP_CHECK(c, hipMemcpyAsync(ref_idx, s->ref_idx, n, hipMemcpyDeviceToHost, c->stream));
-  if (mv) JM_HIP_CHECK(c, hipMemcpyAsync(mv, s->mv, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ref_idx) JM_HIP_CHECK(c, hipMemcpyAsync(ref_idx, s->ref_idx.ptr, n, hipMemcpyDeviceToHost, c->stream));
+  if (mv) JM_HIP_CHECK(c, hipMemcpyAsync(mv, s->mv.ptr, n * 4, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -2728,9 +2807,9 @@ extern "C" int jmhip_epzs_map_upload(jmhip_ctx *c, const int16_t *map, int searc
   if (rc) return rc;
   const int side = 2 * search_range + 1;
   const uint32_t count = (uint16_t)blk_count;
-  JM_HIP_CHECK(c, hipMemsetAsync(s->ep_map, 0, sizeof(uint16_t) * s->ep_cells, c->stream));
-  if (map) JM_HIP_CHECK(c, hipMemcpyAsync(s->ep_map, map, sizeof(int16_t) * side * side, hipMemcpyHostToDevice, c->stream));
-  JM_HIP_CHECK(c, hipMemcpyAsync(s->ep_count, &count, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, fill(c, s->ep.map, 0));
+  if (map) JM_HIP_CHECK(c, hipMemcpyAsync(s->ep.map.ptr, map, sizeof(int16_t) * side * side, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(s->ep.count.ptr, &count, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -2742,9 +2821,9 @@ extern "C" int jmhip_epzs_map_info(jmhip_ctx *c, int *aliased_tests, uint32_t *s
   if (aliased_tests) *aliased_tests = s->ep_aliases;
   if (searches) {
     *searches = 0;
-    if (s->ep_count) {
+    if (s->ep.count.ptr) {
       JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-      JM_HIP_CHECK(c, hipMemcpyAsync(searches, s->ep_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      JM_HIP_CHECK(c, hipMemcpyAsync(searches, s->ep.count.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
       JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     }
   }
@@ -2838,7 +2917,7 @@ static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, i
       if (dev >= 0 && dev < 64) part_uploaded[dev] = true;
     }
   }
-  slice_to_frame_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(s->out, s->ref8ts, mb_first, n, c->mbw, sm, (jmhip_me_mb *)c->me_jobs_dev,
+  slice_to_frame_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(s->out.as<jmhip_mb_inter>(), s->ref8ts.as<int>(), mb_first, n, c->mbw, sm, (jmhip_me_mb *)c->me_jobs_dev,
                                                                 (jmhip_me_result *)c->me_res_dev, (jmhip_mb_mode *)c->fr_modes + n, (int8_t *)c->fr_blk_ref, form);
   JM_HIP_CHECK(c, hipGetLastError());
   // the search-stage arrays now hold this picture; a resident re-run of jmhip_me_frame on them is meaningless and is refused (geometry check)
@@ -2853,16 +2932,14 @@ extern "C" int jmhip_slice_ref8ts_download(jmhip_ctx *c, int32_t *ref8ts, int mb
   if (!c || !ref8ts || mb_first < 0 || mb_count < 1 || mb_first + mb_count > c->mbw * c->mbh || !c->slice_state) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_slice_ref8ts_download: arguments") : JMHIP_ERR_ARG;
   SliceState *s = static_cast<SliceState *>(c->slice_state);
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  JM_HIP_CHECK(c, hipMemcpyAsync(ref8ts, s->ref8ts + (size_t)mb_first * 4, sizeof(int32_t) * 4 * (size_t)mb_count, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(ref8ts, s->ref8ts.as<int>() + (size_t)mb_first * 4, sizeof(int32_t) * 4 * (size_t)mb_count, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
 
 void jm_slice_state_free(jmhip_ctx *c)
 {
-  SliceState *s = static_cast<SliceState *>(c->slice_state);
-  if (!s) return;
-  slice_state_release(s);
+  delete static_cast<SliceState *>(c->slice_state);
   c->slice_state = nullptr;
 }
 

@@ -801,35 +801,46 @@ void launch_sim(bool ffs, bool chain, int nr, int grid, hipStream_t st, const XD
   else { if (chain) launch_sim_refs<false, true>(nr, grid, lds, st, D); else launch_sim_refs<false, false>(nr, grid, lds, st, D); }
 }
 
+int x_cap(int nmb) { return (nmb + JM_SHARDS - 1) / JM_SHARDS; }      // macroblocks per shard
+
+// every device buffer is a DevBuf: allocated and sized in alloc() only, freed with the state
 struct XState {
-  jmhip_me_mb *jobs = nullptr; jmhip_me_result *res = nullptr;
-  unsigned long long *valid_rec = nullptr, *need_rec = nullptr;
-  XSkip *skip = nullptr;
-  uint8_t *pending = nullptr, *chg[2] = {nullptr, nullptr};
-  int *items = nullptr, *sub_list = nullptr, *skip_list = nullptr, *cnt = nullptr;
-  MeDev *medev = nullptr;                        // the frame kernels' parameter block in device memory (their list form re-reads it per item)
+  DevBuf jobs, res;                              // jmhip_me_mb / jmhip_me_result [XR][nmb]
+  DevBuf valid_rec, need_rec;                    // unsigned long long [XR][nmb]
+  DevBuf skip;                                   // XSkip [nmb]
+  DevBuf pending, chg[2];                        // uint8_t [nmb]
+  DevBuf items, sub_list, skip_list, cnt;        // int: the sharded work lists and every sweep's counters
+  DevBuf medev;                                  // the frame kernels' parameter block in device memory (their list form re-reads it per item)
   // the sweeps' flag words arrive in page-locked host memory one sweep behind the launches (no host wait between sweeps): two ints per sweep, an event each
   int *h_flags = nullptr; hipEvent_t evt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int nmb = 0, refs = 0;
+  XState() = default;
+  XState(const XState &) = delete;
+  XState &operator=(const XState &) = delete;
+  ~XState()
+  {
+    if (h_flags) (void)hipHostFree(h_flags);
+    for (hipEvent_t e : evt) if (e) (void)hipEventDestroy(e);
+  }
+  bool alloc(int n)
+  {
+    nmb = n; refs = XR;
+    const size_t nj = (size_t)XR * nmb, shard_mbs = (size_t)JM_SHARDS * x_cap(nmb);
+    bool ok = jobs.alloc(sizeof(jmhip_me_mb) * nj) && res.alloc(sizeof(jmhip_me_result) * nj) && valid_rec.alloc(8 * nj) && need_rec.alloc(8 * nj) &&
+              skip.alloc(sizeof(XSkip) * nmb) && pending.alloc(nmb) && chg[0].alloc(nmb) && chg[1].alloc(nmb) &&
+              items.alloc(sizeof(int) * shard_mbs * XR * JMHIP_NPART) && sub_list.alloc(sizeof(int) * shard_mbs * XR) && skip_list.alloc(sizeof(int) * shard_mbs) &&
+              cnt.alloc(sizeof(int) * (size_t)X_CNT_SWEEP * (X_MAX_SWEEPS + 1)) && medev.alloc(sizeof(MeDev)) &&
+              hipHostMalloc((void **)&h_flags, sizeof(int) * 2 * (X_MAX_SWEEPS + 1), hipHostMallocDefault) == hipSuccess;
+    for (int k = 0; ok && k < 8; k++) ok = hipEventCreateWithFlags(&evt[k], hipEventDisableTiming) == hipSuccess;
+    return ok;
+  }
 };
-
-int x_cap(int nmb) { return (nmb + JM_SHARDS - 1) / JM_SHARDS; }      // macroblocks per shard
-
-void x_release(XState *x)
-{
-  void *bufs[] = {x->jobs, x->res, x->valid_rec, x->need_rec, x->skip, x->pending, x->chg[0], x->chg[1], x->items, x->sub_list, x->skip_list, x->cnt, x->medev};
-  for (void *b : bufs) if (b) (void)hipFree(b);
-  if (x->h_flags) (void)hipHostFree(x->h_flags);
-  for (hipEvent_t e : x->evt) if (e) (void)hipEventDestroy(e);
-  delete x;
-}
 
 }  // namespace
 
 void jm_xslice_free(jmhip_ctx *c)
 {
-  if (!c->xslice_state) return;
-  x_release(static_cast<XState *>(c->xslice_state));
+  delete static_cast<XState *>(c->xslice_state);
   c->xslice_state = nullptr;
 }
 
@@ -850,33 +861,12 @@ int jm_xslice_run(jmhip_ctx *c, const jmhip_slice_params *prm, int8_t *ref_idx, 
   *settled = 0;
   XState *x = static_cast<XState *>(c->xslice_state);
   if (x && (x->nmb != nmb || x->refs < nr)) { jm_xslice_free(c); x = nullptr; }
-  bool fresh = false;
   if (!x) {
     x = new XState();
-    x->nmb = nmb; x->refs = XR;
-    const size_t nj = (size_t)XR * nmb;
-    bool ok = hipMalloc((void **)&x->jobs, sizeof(jmhip_me_mb) * nj) == hipSuccess && hipMalloc((void **)&x->res, sizeof(jmhip_me_result) * nj) == hipSuccess &&
-              hipMalloc((void **)&x->valid_rec, 8 * nj) == hipSuccess && hipMalloc((void **)&x->need_rec, 8 * nj) == hipSuccess &&
-              hipMalloc((void **)&x->skip, sizeof(XSkip) * nmb) == hipSuccess && hipMalloc((void **)&x->pending, nmb) == hipSuccess &&
-              hipMalloc((void **)&x->chg[0], nmb) == hipSuccess && hipMalloc((void **)&x->chg[1], nmb) == hipSuccess &&
-              hipMalloc((void **)&x->items, sizeof(int) * (size_t)JM_SHARDS * x_cap(nmb) * XR * JMHIP_NPART) == hipSuccess &&
-              hipMalloc((void **)&x->sub_list, sizeof(int) * (size_t)JM_SHARDS * x_cap(nmb) * XR) == hipSuccess &&
-              hipMalloc((void **)&x->skip_list, sizeof(int) * (size_t)JM_SHARDS * x_cap(nmb)) == hipSuccess &&
-              hipMalloc((void **)&x->cnt, sizeof(int) * (size_t)X_CNT_SWEEP * (X_MAX_SWEEPS + 1)) == hipSuccess &&
-              hipMalloc((void **)&x->medev, sizeof(MeDev)) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&x->h_flags, sizeof(int) * 2 * (X_MAX_SWEEPS + 1), hipHostMallocDefault) == hipSuccess;
-    for (int k = 0; ok && k < 8; k++) ok = hipEventCreateWithFlags(&x->evt[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok) { x_release(x); return jm_fail(c, JMHIP_ERR_NOMEM, "record arrays of the exhaustive slice search"); }
-    JM_HIP_CHECK(c, hipMemsetAsync(x->jobs, 0, sizeof(jmhip_me_mb) * nj, c->stream));
-    JM_HIP_CHECK(c, hipMemsetAsync(x->res, 0, sizeof(jmhip_me_result) * nj, c->stream));
-    JM_HIP_CHECK(c, hipMemsetAsync(x->skip, 0, sizeof(XSkip) * nmb, c->stream));
-    JM_HIP_CHECK(c, hipMemsetAsync(x->pending, 0, nmb, c->stream));
-    JM_HIP_CHECK(c, hipMemsetAsync(x->chg[0], 0, nmb, c->stream));
-    JM_HIP_CHECK(c, hipMemsetAsync(x->chg[1], 0, nmb, c->stream));
+    if (!x->alloc(nmb)) { delete x; return jm_fail(c, JMHIP_ERR_NOMEM, "record arrays of the exhaustive slice search"); }
+    for (const DevBuf *b : {&x->jobs, &x->res, &x->skip, &x->pending, &x->chg[0], &x->chg[1]}) JM_HIP_CHECK(c, hipMemsetAsync(b->ptr, 0, b->bytes, c->stream));
     c->xslice_state = x;
-    fresh = true;
   }
-  (void)fresh;
   {
     static bool uploaded[64] = {false};
     const int dev = c->cfg.device;
@@ -902,7 +892,7 @@ int jm_xslice_run(jmhip_ctx *c, const jmhip_slice_params *prm, int8_t *ref_idx, 
   P.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
   P.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
   if ((rc = jm_me_pair_geometry(c, prm->search_range, &P, &plds))) return rc;
-  JM_HIP_CHECK(c, hipMemcpyAsync(x->medev, &P, sizeof(MeDev), hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(x->medev.ptr, &P, sizeof(MeDev), hipMemcpyHostToDevice, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (P is a stack object)
 
   XDev D{};
@@ -917,13 +907,14 @@ int jm_xslice_run(jmhip_ctx *c, const jmhip_slice_params *prm, int8_t *ref_idx, 
   D.W = c->W; D.H = c->H; D.Wp = c->Wp; D.Hp = c->Hp; D.mbw = c->mbw; D.mbh = c->mbh; D.w4 = c->W / 4; D.nmb = nmb;
   D.cur = c->cur_y; D.ref_sub = P.ref_sub;
   D.ref_idx = ref_idx; D.mv = mv; D.out = out;
-  D.jobs = x->jobs; D.res = x->res; D.valid_rec = x->valid_rec; D.need_rec = x->need_rec; D.skip = x->skip; D.pending = x->pending;
-  D.items = x->items; D.sub_list = x->sub_list; D.skip_list = x->skip_list; D.cnt = x->cnt;
+  D.jobs = x->jobs.as<jmhip_me_mb>(); D.res = x->res.as<jmhip_me_result>(); D.valid_rec = x->valid_rec.as<unsigned long long>(); D.need_rec = x->need_rec.as<unsigned long long>();
+  D.skip = x->skip.as<XSkip>(); D.pending = x->pending.as<uint8_t>();
+  D.items = x->items.as<int>(); D.sub_list = x->sub_list.as<int>(); D.skip_list = x->skip_list.as<int>(); D.cnt = x->cnt.as<int>();
   D.cap_items = x_cap(nmb) * XR * JMHIP_NPART; D.cap_sub = x_cap(nmb) * XR; D.cap_skip = x_cap(nmb);
 
   x_jobs_init_kernel<<<(nr * nmb + 255) / 256, 256, 0, c->stream>>>(D);       // (the reference slots of a list index may differ from call to call)
   const int cap = std::min(X_MAX_SWEEPS, getenv("JMHIP_SLICE_SWEEPS") ? atoi(getenv("JMHIP_SLICE_SWEEPS")) : 400);
-  JM_HIP_CHECK(c, hipMemsetAsync(x->cnt, 0, sizeof(int) * (size_t)X_CNT_SWEEP * (cap + 1), c->stream));      // every sweep has its own counters: one clear per call
+  JM_HIP_CHECK(c, hipMemsetAsync(x->cnt.ptr, 0, sizeof(int) * (size_t)X_CNT_SWEEP * (cap + 1), c->stream));      // every sweep has its own counters: one clear per call
   const int check_every = getenv("JMHIP_SLICE_CHECK") ? std::max(1, atoi(getenv("JMHIP_SLICE_CHECK"))) : 1;
   const bool trace = getenv("JMHIP_SLICE_TRACE") != nullptr;
   const bool ffs = prm->search_mode == JMHIP_SEARCH_FASTFULL;
@@ -938,9 +929,9 @@ int jm_xslice_run(jmhip_ctx *c, const jmhip_slice_params *prm, int8_t *ref_idx, 
   const int chain_budget = getenv("JMHIP_X_CHAIN_BUDGET") ? std::max(1, atoi(getenv("JMHIP_X_CHAIN_BUDGET"))) : (nr == 1 ? JMHIP_NPART : 4);
   const int chain_from = getenv("JMHIP_X_CHAIN_FROM") ? atoi(getenv("JMHIP_X_CHAIN_FROM")) : (ffs ? (1 << 30) : 5);
   for (; sweep < cap; sweep++) {
-    int *cnt = x->cnt + (size_t)X_CNT_SWEEP * sweep;
+    int *cnt = x->cnt.as<int>() + (size_t)X_CNT_SWEEP * sweep;
     D.cnt = cnt; D.stats = trace; D.debug = getenv("JMHIP_X_DEBUG") ? atoi(getenv("JMHIP_X_DEBUG")) : 0;
-    D.first_sweep = sweep == 0; D.chg_prev = x->chg[sweep & 1]; D.chg_next = x->chg[(sweep + 1) & 1];
+    D.first_sweep = sweep == 0; D.chg_prev = x->chg[sweep & 1].as<uint8_t>(); D.chg_next = x->chg[(sweep + 1) & 1].as<uint8_t>();
     D.chain_budget = chain_budget;
     // The first sweeps ask for nearly every record of nearly every macroblock: the frame kernels compute them at their full rate over work lists.
     // Once few macroblocks still ask (chain_from), the replay computes what it misses in place and a sweep resolves a macroblock's whole chain;
@@ -953,8 +944,8 @@ int jm_xslice_run(jmhip_ctx *c, const jmhip_slice_params *prm, int8_t *ref_idx, 
       if (const char *e = getenv("JMHIP_X_GRID")) big = small = std::max(8, atoi(e) & ~7);        // experiments: few workgroups, many trips each
       const bool wide = !chain && sweep < 3;
       {
-        jm_launch_me_pair_list(c, P, x->medev, plds, x->jobs, x->items, x->res, cnt, D.cap_items, wide ? big : small);
-        jm_launch_me_sub_list(c, P, x->jobs, x->res, x->sub_list, x->need_rec, cnt + X_CNT_LIST, D.cap_sub, wide ? std::min(big, jm_xcd_grid(nr * prm->mb_count)) : small);
+        jm_launch_me_pair_list(c, P, x->medev.as<MeDev>(), plds, D.jobs, D.items, D.res, cnt, D.cap_items, wide ? big : small);
+        jm_launch_me_sub_list(c, P, D.jobs, D.res, D.sub_list, D.need_rec, cnt + X_CNT_LIST, D.cap_sub, wide ? std::min(big, jm_xcd_grid(nr * prm->mb_count)) : small);
       }
       if (!chain && !prm->rdopt) x_skip_kernel<<<wide ? std::max(1, prm->mb_count / 4) : 256, 64, 0, c->stream>>>(D);
     }
