@@ -645,7 +645,7 @@ extern "C" int jmhip_bipred_search(jmhip_ctx *c, const jmhip_bipred_params *prm,
     if (j.stage == 0 && j.search_range > maxR) maxR = j.search_range;
     for (int k = 0; k < 2; k++) if (j.mv[k] < -8192 || j.mv[k] > 8192 || j.s_mv[k] < -8192 || j.s_mv[k] > 8192) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_search: vector out of range");
   }
-  for (int k = 0; k < 3; k++) if (prm->lambda[k] < 0 || prm->lambda[k] > 4000000) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_search: lambda factor out of the packed key range");
+  for (int k = 0; k < 3; k++) if (prm->lambda[k] < 0 || prm->lambda[k] > JMHIP_LAMBDA_MAX_BIPRED) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_search: lambda factor out of the packed key range");
   if (prm->apply_weights && (prm->luma_log_weight_denom < 0 || prm->luma_log_weight_denom > 14)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_search: weight denominator");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_ensure_ref_table(c);
@@ -689,7 +689,7 @@ extern "C" int jmhip_bipred_chain(jmhip_ctx *c, const jmhip_bipred_chain_params 
     // pel units: the chain moves a vector by less than 2 * search_range, and the quarter-pel results must fit 16 bits
     for (int k = 0; k < 2; k++) if (j.mv[k] < -4096 || j.mv[k] > 4096 || j.s_mv[k] < -4096 || j.s_mv[k] > 4096) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: vector out of range");
   }
-  for (int k = 0; k < 3; k++) if (prm->lambda[k] < 0 || prm->lambda[k] > 4000000) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_chain: lambda factor out of the packed key range");
+  for (int k = 0; k < 3; k++) if (prm->lambda[k] < 0 || prm->lambda[k] > JMHIP_LAMBDA_MAX_BIPRED) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_bipred_chain: lambda factor out of the packed key range");
   if (prm->apply_weights && (prm->luma_log_weight_denom < 0 || prm->luma_log_weight_denom > 14)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_bipred_chain: weight denominator");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_ensure_ref_table(c);

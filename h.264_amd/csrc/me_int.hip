@@ -1529,7 +1529,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
   jmhip_me_params eff = *prm;
   if (!eff.metric_set) { eff.metric[0] = 0; eff.metric[1] = eff.metric[2] = 2; eff.chroma_me = 0; eff.metric_set = 1; }
   for (int k = 0; k < 3; k++)
-    if (prm->lambda[k] < 0 || prm->lambda[k] >= (1 << 24)) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_me_frame: lambda factor must be below 2^24 (the kernels multiply it with __umul24; JM's largest, QP 51, is 5.5e6)");
+    if (prm->lambda[k] < 0 || prm->lambda[k] > JMHIP_LAMBDA_MAX_ME_FRAME) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_me_frame: lambda factor must be below 2^24 (the kernels multiply it with __umul24; JM's largest, QP 51, is 5.5e6)");
   if (!c->has_cur) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: current picture not uploaded");
   if (!(prm->partition_mask & ((1ull << JMHIP_NPART) - 1))) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: empty partition mask");
   if (prm->wp_enable && (prm->wp_denom < 0 || prm->wp_denom > 7 || prm->wp_round < 0 || prm->wp_round > 64)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: weighted-prediction denominator / rounding out of range");

@@ -299,7 +299,7 @@ extern "C" int jmhip_me_subpel(jmhip_ctx *c, const jmhip_me_params *prm, const j
         return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_subpel: integer vector out of range");
   }
   for (int k = 0; k < 3; k++)
-    if (prm->lambda[k] < 0 || prm->lambda[k] > 30000000) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_me_subpel: lambda factor out of the 32-bit cost range");
+    if (prm->lambda[k] < 0 || prm->lambda[k] > JMHIP_LAMBDA_MAX_ME_SUBPEL) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_me_subpel: lambda factor out of the 32-bit cost range");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_me_sub_tables(c);
   if (rc) return rc;

@@ -2461,7 +2461,7 @@ static int check_slice_args(jmhip_ctx *c, const jmhip_slice_params *prm)
   if (!c->has_cur) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: current picture not uploaded");
   for (int k = 0; k < 3; k++) {
     if (prm->metric[k] < 0 || prm->metric[k] > 2) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_p_slice_search: ME metrics are SAD (0), SSE (1) or SATD (2)");
-    if (prm->lambda_mf[k] < 0 || prm->lambda_mf[k] >= (1 << 24)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: lambda factor out of range");
+    if (prm->lambda_mf[k] < 0 || prm->lambda_mf[k] > JMHIP_LAMBDA_MAX_SLICE) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_p_slice_search: lambda factor out of range");
   }
   if ((prm->search_mode == JMHIP_SEARCH_FULL || prm->search_mode == JMHIP_SEARCH_FASTFULL) && prm->metric[0] != 0)
     return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_p_slice_search: the exhaustive searches take the SAD metric at full-pel positions");

@@ -165,6 +165,12 @@ TQ_RESULT_DTYPE = np.dtype([("levels", "<i4", (16, 17)), ("runs", "<i4", (16, 17
 MB_MODE_DTYPE = np.dtype([("mode", "i1"), ("b8mode", "i1", (4,)), ("pad", "i1", (3,))])
 TQ_KINDS = {"luma4x4": 0, "luma8x8": 1, "luma16x16": 2, "chroma": 3}
 
+# JMHIP_LAMBDA_MAX_* of include/jmhip.h: the largest Lagrangian factor each search entry accepts at any of its three levels
+LAMBDA_MAX_ME_FRAME = (1 << 24) - 1
+LAMBDA_MAX_SLICE = (1 << 24) - 1
+LAMBDA_MAX_ME_SUBPEL = 30000000
+LAMBDA_MAX_BIPRED = 4000000
+
 
 def load_library():
     """Loads libjmhip.so. Raises (never falls back) when it is missing."""

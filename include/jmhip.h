@@ -144,6 +144,31 @@ void jmhip_partition_info(int p, int *blocktype, int *x4, int *y4, int *w4, int 
 
 enum { JMHIP_SEARCH_FULL = -1, JMHIP_SEARCH_FASTFULL = 0 };   /* input->SearchMode */
 
+/* The largest Lagrangian factor (lambda_factor[] / enc_mb.lambda_mf[], 16 fractional bits) each search entry accepts at any of its three
+ * levels. A larger (or negative) value is refused before anything is launched: JMHIP_ERR_UNSUPPORTED from jmhip_me_frame, jmhip_me_subpel,
+ * jmhip_bipred_search and jmhip_bipred_chain, JMHIP_ERR_ARG from jmhip_p_slice_search.
+ *   ME_FRAME / SLICE  2^24 - 1: the integer kernels form lambda * mvbits with a 24-bit multiply (__umul24). With it the motion cost of a
+ *                     candidate stays below 2^8 * 128, so the packed keys hold: SAD (<= 32640 below 16x16) + motion cost < 2^16 in the
+ *                     32-bit (cost << 16 | tie) keys, and SAD (<= 65280) + motion cost + the zero-vector bias < 2^17 in the 16x16 key
+ *                     (cost + bias) << 13 | tie.
+ *   ME_SUBPEL         30 000 000: lambda * (mvbits(dx) + mvbits(dy)) is a 32-bit product, as in JM's WEIGHTED_COST; quarter-pel
+ *                     differences below 2^16 give at most 66 bits, and 30e6 * 66 < 2^31.
+ *   BIPRED            4 000 000: the bi-predictive integer step packs (cost << 13 | spiral position) in 32 bits with cost = SAD + the
+ *                     motion costs of BOTH vectors, so cost < 2^19; vectors up to +-8192 pel cost at most 2 * 66 bits.
+ * What JM itself produces (SetLagrangianMultipliers, src/slice.c:1261; 8-bit video, default lambda parameters, SAD / Hadamard SAD):
+ *   P slices  RDOptimization on:  LAMBDA_FACTOR(sqrt(0.85 * 2^((qp - 12) / 3))) -- 15 105 at QP 0, 5 468 703 at QP 51 (0.68 for 0.85
+ *             when the sequence has B pictures: 4 891 357); RDOptimization off: QP2QUANT[qp - 12] << 16 -- 5 963 776 at QP 51, the largest.
+ *   B slices  RDOptimization on:  LAMBDA_FACTOR(sqrt(0.68 * 2^((qp - 12) / 3) * clip(2, 4, (qp - 12) / 6))) -- 9 782 714 at QP 51, times
+ *             sqrt(0.8) for a B picture that is a reference (8 749 925); 10 937 407 with the 0.85 * 4 form; off: as P slices.
+ * So jmhip_me_frame, jmhip_me_subpel and jmhip_p_slice_search take every factor JM produces for these metrics. jmhip_bipred_search and
+ * jmhip_bipred_chain do not: they refuse B slices from QP 44 on (RDOptimization on; QP 45 for reference B pictures) and from QP 48 on with
+ * RDOptimization off. jmhip_bipred_surface takes no lambda -- its callers add the motion cost on the host -- and refuses none.
+ * With SSE at a level lambda_me is lambda_md itself, not its root: such factors pass 2^24 from QP 37 on (4.3e8 at QP 51) and are refused by every entry. */
+#define JMHIP_LAMBDA_MAX_ME_FRAME  ((1 << 24) - 1)
+#define JMHIP_LAMBDA_MAX_SLICE     ((1 << 24) - 1)
+#define JMHIP_LAMBDA_MAX_ME_SUBPEL 30000000
+#define JMHIP_LAMBDA_MAX_BIPRED    4000000
+
 /* Slice/frame-level inputs of the search (JM: input->, img->, active_pps->). */
 typedef struct {
   int search_mode;         /* JMHIP_SEARCH_FULL: FullPelBlockMotionSearch (src/me_fullsearch.c:47), centre per
@@ -154,7 +179,8 @@ typedef struct {
   int rdopt;               /* input->rdopt                                                           */
   int is_b_slice;          /* img->type == B_SLICE                                                   */
   int level_mv_min, level_mv_max;   /* LEVELMVLIMIT[img->LevelIndex][0..1], inc/mv-search.h:35-54    */
-  int lambda[3];           /* lambda_factor[F_PEL,H_PEL,Q_PEL] (src/slice.c:1329-1358)                */
+  int lambda[3];           /* lambda_factor[F_PEL,H_PEL,Q_PEL] (src/slice.c:1329-1358), each 0 .. JMHIP_LAMBDA_MAX_ME_FRAME
+                              (jmhip_me_subpel: .. JMHIP_LAMBDA_MAX_ME_SUBPEL)                        */
   int transform8x8_mode;   /* input->Transform8x8Mode: SATD uses the 8x8 Hadamard for block types <= 4 */
   int subpel;              /* !input->DisableSubpelME                                                 */
   uint64_t partition_mask; /* bit p set: partition p is searched (all 41: (1<<41)-1)                  */
@@ -256,7 +282,7 @@ typedef struct {
 } jmhip_bipred_job;
 typedef struct { int16_t mv[2]; int32_t cost; } jmhip_bipred_result;
 typedef struct {
-  int lambda[3];             /* lambda_factor[F_PEL, H_PEL, Q_PEL]                                              */
+  int lambda[3];             /* lambda_factor[F_PEL, H_PEL, Q_PEL], each 0 .. JMHIP_LAMBDA_MAX_BIPRED                      */
   int transform8x8_mode;     /* 8x8 Hadamard in stage 1 (test8x8transform for block type 1)                     */
   int apply_weights;         /* active_pps->weighted_bipred_idc > 0                                             */
   int weight1, weight2, offset_bi, wp_luma_round, luma_log_weight_denom;
@@ -278,7 +304,7 @@ typedef struct {
   int16_t pred_a[2], pred_b[2];    /* quarter-pel: pred_mv of `list`, pred_mv_bi of the other list (:880)                          */
 } jmhip_bipred_chain_job;
 typedef struct {
-  int32_t lambda[3];               /* lambda_factor[F_PEL, H_PEL, Q_PEL]                                                           */
+  int32_t lambda[3];               /* lambda_factor[F_PEL, H_PEL, Q_PEL], each 0 .. JMHIP_LAMBDA_MAX_BIPRED                        */
   int32_t transform8x8_mode;       /* 8x8 Hadamard in the sub-pel calls (test8x8transform for block type 1)                        */
   int32_t apply_weights;           /* active_pps->weighted_bipred_idc > 0                                                          */
   int32_t weight_a, weight_b;      /* weight1 / weight2 of the FIRST call: wbp_weight of `list` and of list ^ 1                    */
@@ -369,7 +395,7 @@ typedef struct jmhip_slice_params {
   int32_t num_refs;                        /* listXsize[LIST_0] */
   int32_t ref_slot[JMHIP_SLICE_REFS];      /* list-0 index -> reference slot of the context */
   int32_t valid[8];                        /* enc_mb.valid[1..7] (input->InterSearch[0][..]); [1] must be set */
-  int32_t lambda_mf[3];                    /* enc_mb.lambda_mf[F_PEL, H_PEL, Q_PEL] */
+  int32_t lambda_mf[3];                    /* enc_mb.lambda_mf[F_PEL, H_PEL, Q_PEL], each 0 .. JMHIP_LAMBDA_MAX_SLICE */
   int32_t ref_cost1;                       /* (int)(2 * enc_mb.lambda_me[Q_PEL]): cost of ref > 0 when rdopt = 0 (mode_decision.c:276) */
   int32_t md_metric;                       /* input->ModeDecisionMetric (skip cost): 0 SAD, 2 SATD */
   int32_t metric[3];                       /* input->MEErrorMetric[F_PEL, H_PEL, Q_PEL]: 0 SAD, 2 SATD */

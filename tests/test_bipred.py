@@ -46,6 +46,29 @@ def oracle_bipred(rp1, rp2, cur16, job, lam, t8x8, wp):
     return int(mv[0]), int(mv[1]), cost
 
 
+def make_jobs(dtype, rng, mbw, mbh):
+    """two jobs per macroblock, integer (stage 0) and sub-pel (stage 1) calls alternating, then eight that push both blocks outside the picture"""
+    jobs = np.zeros(2 * mbw * mbh + 8, dtype=dtype)
+    for i in range(len(jobs)):
+        j = jobs[i]
+        j["mb_x"], j["mb_y"] = (i // 2) % mbw, ((i // 2) // mbw) % mbh
+        j["ref1"], j["ref2"] = (0, 1) if i % 3 else (1, 0)
+        j["stage"] = i % 2
+        far = 30 if i >= 2 * mbw * mbh else 6          # the last jobs push both blocks outside the picture (UMV)
+        if j["stage"] == 0:
+            j["s_mv"] = rng.integers(-far, far + 1, 2)
+            j["mv"] = rng.integers(-far, far + 1, 2)
+            j["search_range"] = [16, 8, 4, 2][i % 4]
+            j["min_mcost"] = 2147483647 if i % 5 else 1500   # a carried minimum most candidates cannot beat
+        else:
+            j["s_mv"] = rng.integers(-4 * far, 4 * far + 1, 2)
+            j["mv"] = 4 * rng.integers(-far, far + 1, 2)
+            j["min_mcost"] = 2147483647
+        j["pred1"] = rng.integers(-12, 13, 2)
+        j["pred2"] = rng.integers(-12, 13, 2)
+    return jobs
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("t8x8,wp", [(0, None), (1, None), (0, (37, 29, -3, 16, 5)), (1, (64, 64, 2, 32, 6)), (0, (1, 1, 0, 0, 0))])
 def test_bipred_search(pkg, t8x8, wp):
@@ -67,25 +90,7 @@ def test_bipred_search(pkg, t8x8, wp):
     if wp:
         prm.apply_weights = 1
         prm.weight1, prm.weight2, prm.offset_bi, prm.wp_luma_round, prm.luma_log_weight_denom = wp
-    mbw, mbh = w // 16, h // 16
-    jobs = np.zeros(2 * mbw * mbh + 8, dtype=BIPRED_JOB_DTYPE)
-    for i in range(len(jobs)):
-        j = jobs[i]
-        j["mb_x"], j["mb_y"] = (i // 2) % mbw, ((i // 2) // mbw) % mbh
-        j["ref1"], j["ref2"] = (0, 1) if i % 3 else (1, 0)
-        j["stage"] = i % 2
-        far = 30 if i >= 2 * mbw * mbh else 6          # the last jobs push both blocks outside the picture (UMV)
-        if j["stage"] == 0:
-            j["s_mv"] = rng.integers(-far, far + 1, 2)
-            j["mv"] = rng.integers(-far, far + 1, 2)
-            j["search_range"] = [16, 8, 4, 2][i % 4]
-            j["min_mcost"] = 2147483647 if i % 5 else 1500   # a carried minimum most candidates cannot beat
-        else:
-            j["s_mv"] = rng.integers(-4 * far, 4 * far + 1, 2)
-            j["mv"] = 4 * rng.integers(-far, far + 1, 2)
-            j["min_mcost"] = 2147483647
-        j["pred1"] = rng.integers(-12, 13, 2)
-        j["pred2"] = rng.integers(-12, 13, 2)
+    jobs = make_jobs(BIPRED_JOB_DTYPE, rng, w // 16, h // 16)
     got = ctx.bipred_search(prm, jobs)
     ctx.close()
     rp = [oracle.RefPic(ref1, yuv_format=0), oracle.RefPic(ref2, yuv_format=0)]

@@ -96,16 +96,21 @@ def synth_clip(rng, W, H, nframes):
     return load_pkg().slice_host.synth_clip(rng, W, H, nframes)
 
 
-def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=(0, 2, 2), qp=28, max_mbs=None, t8=0, cavlc=1, wp=None, one_call=False, rdopt=0, map_log=None, map_init=None, what_if=None, ideal_map=False, first_touch=None, md_metric=2, q8=None):
-    """Frames 1.. are coded as P pictures against the previous `nref` SOURCE frames (the search does not care where a reference came from)."""
+def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=(0, 2, 2), qp=28, max_mbs=None, t8=0, cavlc=1, wp=None, one_call=False, rdopt=0, map_log=None, map_init=None, what_if=None, ideal_map=False, first_touch=None, md_metric=2, q8=None, lambda_mf=None, clip=None, oracle_only=False):
+    """Frames 1.. are coded as P pictures against the previous `nref` SOURCE frames (the search does not care where a reference came from).
+    lambda_mf: the three factors when they are to differ (tests/lambda_cases.py); clip: the frames, for pictures other than synth_clip's.
+    oracle_only (with what_if): no device is touched and `pkg` is not used -- the oracle's records alone, for tests that run without a GPU."""
+    assert not oracle_only or (what_if is not None and map_init is None and not one_call)
     rng = np.random.default_rng(seed)
-    clip = synth_clip(rng, W, H, nframes + nref - 1)
+    if clip is None:
+        clip = synth_clip(rng, W, H, nframes + nref - 1)
     lam = int(65536 * np.sqrt(0.85 * 2 ** ((qp - 12) / 3.0) * (4 if False else 1)) + 0.5)     # any positive factor does
-    lam3 = [lam, lam, lam]
+    lam3 = [lam, lam, lam] if lambda_mf is None else list(lambda_mf)
     ref_cost1 = int(2 * np.sqrt(0.85 * 2 ** ((qp - 12) / 3.0)))
     nmb = (W // 16) * (H // 16)
-    ctx = pkg.Context(W, H, yuv_format=0, max_refs=nref, search_range=R)
-    ctx.slice_state_reset()
+    ctx = None if oracle_only else pkg.Context(W, H, yuv_format=0, max_refs=nref, search_range=R)
+    if ctx:
+        ctx.slice_state_reset()
     epzs = oracle.Epzs(W, H, R, nref) if mode == 3 else None
     if map_init is not None:                             # EPZSMap / EPZSBlkCount of an encoder that is already running
         ctx.epzs_map_upload(map_init[0], R, map_init[1])
@@ -115,20 +120,22 @@ def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=
     umhex = oracle.Umhex(W, H, R, nref, qp) if mode == 1 else None
     all_mv_state = np.zeros((4, 4, oracle.MAX_REFS, 9, 2), np.int16)
     prev_field = [(np.zeros((H // 4, W // 4, 2), np.int16), np.full((H // 4, W // 4), -1, np.int64))] * 2
-    lib = pkg.load_library()
+    lib = None if oracle_only else pkg.load_library()
     passes = []
     for f in range(nref, nref + nframes - 1):
         cur = clip[f]
         refs = [clip[f - 1 - r] for r in range(nref)]
         pocs = [2 * (f - 1 - r) for r in range(nref)]
         orefs = [oracle.RefPic(r, yuv_format=0) for r in refs]
-        for r in range(nref):
+        for r in range(nref if ctx else 0):
             ctx.ref_upload(r, refs[r])
             ctx.interp_luma(r)
-        ctx.cur_upload(cur)
+        if ctx:
+            ctx.cur_upload(cur)
         if epzs:
             epzs.slice_init(2 * f, pocs, pocs, [prev_field[0][0], prev_field[1][0]], [prev_field[0][1], prev_field[1][1]])
-            ctx.epzs_colocated_upload(oracle.epzs_colocated(epzs, W, H))
+            if ctx:
+                ctx.epzs_colocated_upload(oracle.epzs_colocated(epzs, W, H))
         ref_idx = np.full((H // 4, W // 4), -1, np.int8)
         mvf = np.zeros((H // 4, W // 4, 2), np.int16)
         per = (nmb + slices - 1) // slices
@@ -184,7 +191,8 @@ def run_synthetic(pkg, mode, W, H, R, nref, slices=1, nframes=3, seed=5, metric=
         epzs.close()
     if umhex:
         umhex.close()
-    ctx.close()
+    if ctx:
+        ctx.close()
     return passes
 
 
