@@ -697,10 +697,10 @@ extern "C" int jmhip_recon_upload(jmhip_ctx *c, const void *Y, const void *U, co
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = ensure_recon(c);
   if (rc) return rc;
-  if ((rc = jm_upload_plane(c, c->rec_y, Y, c->W, c->H, pel_bytes, c->W, 0))) return rc;
+  if ((rc = jm_upload_plane(c, c->rec_y.as<uint8_t>(), Y, c->W, c->H, pel_bytes, c->W, 0))) return rc;
   if (c->Wc) {
-    if ((rc = jm_upload_plane(c, c->rec_u, U, c->Wc, c->Hc, pel_bytes, c->Wc, 0))) return rc;
-    if ((rc = jm_upload_plane(c, c->rec_v, V, c->Wc, c->Hc, pel_bytes, c->Wc, 0))) return rc;
+    if ((rc = jm_upload_plane(c, c->rec_u.as<uint8_t>(), U, c->Wc, c->Hc, pel_bytes, c->Wc, 0))) return rc;
+    if ((rc = jm_upload_plane(c, c->rec_v.as<uint8_t>(), V, c->Wc, c->Hc, pel_bytes, c->Wc, 0))) return rc;
   }
   c->rec_has_pic = true; c->rec_valid = true;
   return JMHIP_OK;
@@ -716,13 +716,8 @@ int dbk_arrays(jmhip_ctx *c, DbkArrays *a)
   const size_t mb_bytes = sizeof(jmhip_deblock_mb) * (size_t)nmb, blk_bytes = sizeof(jmhip_deblock_blk) * (size_t)nmb * 16;
   const size_t blk_off = (mb_bytes + 255) & ~(size_t)255, edge_off = (blk_off + blk_bytes + 255) & ~(size_t)255;
   const size_t total = edge_off + sizeof(EdgeInfo) * (size_t)nmb * 8;
-  if (c->dbk_cap < total) {
-    if (c->dbk_dev) JM_HIP_CHECK(c, hipFree(c->dbk_dev));
-    c->dbk_dev = nullptr; c->dbk_cap = 0;
-    if (hipMalloc(&c->dbk_dev, total) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "deblocking arrays");
-    c->dbk_cap = total;
-  }
-  a->mbs = (uint8_t *)c->dbk_dev; a->blks = a->mbs + blk_off; a->edges = a->mbs + edge_off;
+  if (!c->dbk_dev.grow(total)) return jm_fail(c, JMHIP_ERR_NOMEM, "deblocking arrays");
+  a->mbs = c->dbk_dev.as<uint8_t>(); a->blks = a->mbs + blk_off; a->edges = a->mbs + edge_off;
   return JMHIP_OK;
 }
 
@@ -743,16 +738,11 @@ int dbk_run(jmhip_ctx *c, const DbkArrays &a, int mvlimit, int mb_row0, int mb_r
       const size_t rec_bytes = rcf == 2 ? DbrGeo<2>::REC : rcf == 1 ? DbrGeo<1>::REC : DbrGeo<0>::REC;
       const int nrange = c->mbw * mb_rows;
       const size_t st_bytes = (size_t)nmb * rec_bytes, need = st_bytes + 2 * (size_t)nmb + 64 * sizeof(int);
-      if (c->dbr_cap < need) {
-        if (c->dbr_dev) JM_HIP_CHECK(c, hipFree(c->dbr_dev));
-        c->dbr_dev = nullptr; c->dbr_cap = 0;
-        if (hipMalloc(&c->dbr_dev, need) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "deblocking records");
-        c->dbr_cap = need;
-      }
-      uint8_t *st = (uint8_t *)c->dbr_dev, *chg = st + st_bytes;
+      if (!c->dbr_dev.grow(need)) return jm_fail(c, JMHIP_ERR_NOMEM, "deblocking records");
+      uint8_t *st = c->dbr_dev.as<uint8_t>(), *chg = st + st_bytes;
       int *counters = reinterpret_cast<int *>(st + ((st_bytes + 2 * (size_t)nmb + 3) & ~(size_t)3));
       DbkRelax R;
-      R.y = c->rec_y; R.u = c->rec_u; R.v = c->rec_v; R.st = st; R.edges = (const EdgeInfo *)a.edges;
+      R.y = c->rec_y.as<uint8_t>(); R.u = c->rec_u.as<uint8_t>(); R.v = c->rec_v.as<uint8_t>(); R.st = st; R.edges = (const EdgeInfo *)a.edges;
       R.W = c->W; R.Wc = c->Wc; R.mbw = c->mbw; R.mbh = c->mbh; R.row0 = mb_row0; R.rows = mb_rows;
       const int cap = getenv("JMHIP_DEBLOCK_SWEEPS") ? atoi(getenv("JMHIP_DEBLOCK_SWEEPS")) : 48, group = 4;     // sweeps per host check
       bool settled = false;
@@ -774,16 +764,16 @@ int dbk_run(jmhip_ctx *c, const DbkArrays &a, int mvlimit, int mb_row0, int mb_r
       }
       c->dbk_sweeps = sweep;
       if (settled) {
-        if (rcf == 2) deblock_compose_kernel<2><<<(nrange + 3) / 4, 64, 0, c->stream>>>(st, c->rec_y, c->rec_u, c->rec_v, c->W, c->Wc, c->mbw, mb_row0, mb_rows);
-        else if (rcf == 1) deblock_compose_kernel<1><<<(nrange + 3) / 4, 64, 0, c->stream>>>(st, c->rec_y, c->rec_u, c->rec_v, c->W, c->Wc, c->mbw, mb_row0, mb_rows);
-        else deblock_compose_kernel<0><<<(nrange + 3) / 4, 64, 0, c->stream>>>(st, c->rec_y, c->rec_u, c->rec_v, c->W, c->Wc, c->mbw, mb_row0, mb_rows);
+        if (rcf == 2) deblock_compose_kernel<2><<<(nrange + 3) / 4, 64, 0, c->stream>>>(st, c->rec_y.as<uint8_t>(), c->rec_u.as<uint8_t>(), c->rec_v.as<uint8_t>(), c->W, c->Wc, c->mbw, mb_row0, mb_rows);
+        else if (rcf == 1) deblock_compose_kernel<1><<<(nrange + 3) / 4, 64, 0, c->stream>>>(st, c->rec_y.as<uint8_t>(), c->rec_u.as<uint8_t>(), c->rec_v.as<uint8_t>(), c->W, c->Wc, c->mbw, mb_row0, mb_rows);
+        else deblock_compose_kernel<0><<<(nrange + 3) / 4, 64, 0, c->stream>>>(st, c->rec_y.as<uint8_t>(), c->rec_u.as<uint8_t>(), c->rec_v.as<uint8_t>(), c->W, c->Wc, c->mbw, mb_row0, mb_rows);
         JM_HIP_CHECK(c, hipGetLastError());
         return JMHIP_OK;
       }
     }
   }
   DeblockDev D;
-  D.y = c->rec_y; D.u = c->rec_u; D.v = c->rec_v;
+  D.y = c->rec_y.as<uint8_t>(); D.u = c->rec_u.as<uint8_t>(); D.v = c->rec_v.as<uint8_t>();
   D.edges = (const EdgeInfo *)a.edges;
   D.W = c->W; D.Wc = c->Wc; D.mbw = c->mbw;
   {
@@ -893,7 +883,7 @@ __global__ __launch_bounds__(256) void deblock_inputs_kernel(const jmhip_me_mb *
 extern "C" int jmhip_deblock_frame(jmhip_ctx *c, const jmhip_deblock_mb *mbs, const jmhip_deblock_blk *blks, int mvlimit, int mb_row0, int mb_rows)
 {
   if (!c || !mbs || !blks) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_frame: NULL argument") : JMHIP_ERR_ARG;
-  if (!c->rec_y || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_frame: no recon picture yet");
+  if (!c->rec_y.ptr || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_frame: no recon picture yet");
   if (mb_rows <= 0) { mb_row0 = 0; mb_rows = c->mbh; }
   if (mb_row0 < 0 || mb_row0 + mb_rows > c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_frame: row band outside the picture");
   if (mvlimit != 4 && mvlimit != 2) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_frame: mvlimit is 4 (frame) or 2 (field)");
@@ -924,7 +914,7 @@ extern "C" int jmhip_deblock_frame(jmhip_ctx *c, const jmhip_deblock_mb *mbs, co
 extern "C" int jmhip_deblock_recon(jmhip_ctx *c, const jmhip_deblock_params *prm)
 {
   if (!c || !prm) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: NULL argument") : JMHIP_ERR_ARG;
-  if (!c->rec_y || c->fr_n <= 0 || c->fr_n != c->me_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: needs the macroblock list of the last jmhip_me_frame + jmhip_residual_frame");
+  if (!c->rec_y.ptr || c->fr_n <= 0 || c->fr_n != c->me_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: needs the macroblock list of the last jmhip_me_frame + jmhip_residual_frame");
   int row0 = prm->mb_row0, rows = prm->mb_rows;
   if (rows <= 0) { row0 = 0; rows = c->mbh; }
   if (row0 < 0 || row0 + rows > c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: row band outside the picture");
@@ -942,9 +932,9 @@ extern "C" int jmhip_deblock_recon(jmhip_ctx *c, const jmhip_deblock_params *prm
   // its first row's top edge is off (idc 2 with slice_rows), exactly as for jmhip_deblock_frame
   JM_HIP_CHECK(c, hipMemsetAsync(a.mbs, 0, (size_t)(a.edges - a.mbs), c->stream));
   (void)nmb;
-  const jmhip_mb_mode *modes = (const jmhip_mb_mode *)c->fr_modes;
+  const jmhip_mb_mode *modes = c->fr_modes.as<const jmhip_mb_mode>();
   const JmMbCoded *coded = reinterpret_cast<const JmMbCoded *>(modes + 2 * (size_t)n);       // layout of jmhip_residual_frame
-  deblock_inputs_kernel<<<(n + 15) / 16, 256, 0, c->stream>>>((const jmhip_me_mb *)c->me_jobs_dev, (const jmhip_me_result *)c->me_res_dev, modes, coded, n,
+  deblock_inputs_kernel<<<(n + 15) / 16, 256, 0, c->stream>>>(c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_res_dev.as<const jmhip_me_result>(), modes, coded, n,
                                                               *prm, c->mbw, (jmhip_deblock_mb *)a.mbs, (jmhip_deblock_blk *)a.blks);
   JM_HIP_CHECK(c, hipGetLastError());
   std::vector<int> starts;

@@ -205,27 +205,27 @@ int jm_frame_buffers_ensure(jmhip_ctx *c, int n)
 {
   { int rc = jm_ensure_recon(c); if (rc) return rc; }
   if (c->fr_capacity >= n) return JMHIP_OK;
-  void **bufs[] = {&c->fr_jobs_y, &c->fr_jobs_c, &c->fr_res_y, &c->fr_res_c, &c->fr_modes, &c->fr_blk_ref, &c->fr_rec};
-  for (auto b : bufs) { if (*b) JM_HIP_CHECK(c, hipFree(*b)); *b = nullptr; }
   c->fr_capacity = 0;
-  // the chroma job tiles are only partly written per frame (mb_cr_size columns/rows): zero the rest once
-  bool ok = hipMalloc(&c->fr_jobs_y, sizeof(jmhip_tq_job) * (size_t)n) == hipSuccess &&
-            hipMalloc(&c->fr_jobs_c, sizeof(jmhip_tq_job) * (size_t)n * 2) == hipSuccess &&
-            hipMalloc(&c->fr_res_y, sizeof(jmhip_tq_result) * (size_t)n) == hipSuccess &&
-            hipMalloc(&c->fr_res_c, sizeof(jmhip_tq_result) * (size_t)n * 2) == hipSuccess &&
-            hipMalloc(&c->fr_modes, (sizeof(jmhip_mb_mode) * 2 + sizeof(JmMbCoded)) * (size_t)n) == hipSuccess &&
-            hipMalloc(&c->fr_blk_ref, 4 * (size_t)n) == hipSuccess &&
-            hipMalloc(&c->fr_rec, (c->cfg.yuv_format == JMHIP_YUV422 ? sizeof(jmhip_mb_residual422) : sizeof(JmMbRes)) * (size_t)n) == hipSuccess;
-  if (!ok) {                                            // leave nothing half-allocated behind (fr_capacity stays 0)
-    for (auto b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-    return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage arrays");
-  }
-  JM_HIP_CHECK(c, hipMemsetAsync(c->fr_jobs_c, 0, sizeof(jmhip_tq_job) * (size_t)n * 2, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(c->fr_res_y, 0, sizeof(jmhip_tq_result) * (size_t)n, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(c->fr_res_c, 0, sizeof(jmhip_tq_result) * (size_t)n * 2, c->stream));
-  if (!c->fr_quant && hipMalloc(&c->fr_quant, sizeof(jmhip_quant) * 4) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage quantisers");
-  c->fr_capacity = n;
-  return JMHIP_OK;
+  // the group: every member with its size, and whether it is zeroed when (re)allocated -- the chroma job tiles are only partly written per frame
+  // (mb_cr_size columns/rows) and the result records only where a kernel has work
+  const struct { DevBuf &buf; size_t bytes; bool zero; } group[] = {
+    {c->fr_jobs_y, sizeof(jmhip_tq_job) * (size_t)n, false},
+    {c->fr_jobs_c, sizeof(jmhip_tq_job) * (size_t)n * 2, true},
+    {c->fr_res_y, sizeof(jmhip_tq_result) * (size_t)n, true},
+    {c->fr_res_c, sizeof(jmhip_tq_result) * (size_t)n * 2, true},
+    {c->fr_modes, (sizeof(jmhip_mb_mode) * 2 + sizeof(JmMbCoded)) * (size_t)n, false},
+    {c->fr_blk_ref, 4 * (size_t)n, false},
+    {c->fr_rec, (c->cfg.yuv_format == JMHIP_YUV422 ? sizeof(jmhip_mb_residual422) : sizeof(JmMbRes)) * (size_t)n, false}};
+  auto release = [&] { for (auto &g : group) g.buf = DevBuf(); };
+  release();                                            // all of the old group before any of the new one, so that peak memory is one group
+  const int rc = [&]() -> int {
+    for (auto &g : group) if (!g.buf.alloc(g.bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage arrays");
+    for (auto &g : group) if (g.zero) JM_HIP_CHECK(c, hipMemsetAsync(g.buf.ptr, 0, g.buf.bytes, c->stream));
+    if (!c->fr_quant.grow(sizeof(jmhip_quant) * 4)) return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage quantisers");
+    return JMHIP_OK;
+  }();
+  if (rc) release(); else c->fr_capacity = n;           // nothing half-made is left behind, and the capacity is set last
+  return rc;
 }
 
 extern "C" int jmhip_frame_wp_set(jmhip_ctx *c, const jmhip_frame_wp *wp)
@@ -249,13 +249,9 @@ extern "C" int jmhip_frame_bipred_set(jmhip_ctx *c, const jmhip_mb_bipred *bi, i
         return jm_fail(c, JMHIP_ERR_ARG, "jmhip_frame_bipred_set: list-1 reference slot 0..3 with quarter-pel planes (jmhip_interp_luma)");
     }
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  if (c->fr_bi_capacity < n) {
-    if (c->fr_bi) JM_HIP_CHECK(c, hipFree(c->fr_bi));
-    c->fr_bi = nullptr; c->fr_bi_capacity = 0;
-    if (hipMalloc(&c->fr_bi, sizeof(jmhip_mb_bipred) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "second-list array of the frame stage");
-    c->fr_bi_capacity = n;
-  }
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->fr_bi, bi, sizeof(jmhip_mb_bipred) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  const size_t bytes = sizeof(jmhip_mb_bipred) * (size_t)n;
+  if (!c->fr_bi.grow(bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "second-list array of the frame stage");
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->fr_bi.ptr, bi, bytes, hipMemcpyHostToDevice, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));             // caller-owned array
   c->fr_bi_n = n; c->fr_bi_mask = 0;
   for (int i = 0; i < n; i++) for (int k = 0; k < 4; k++) if (bi[i].pdir[k]) c->fr_bi_mask |= 1u << bi[i].ref1[k];
@@ -272,7 +268,7 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
 {
   if (!c || !quants || (nquants != 3 && nquants != 4)) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: NULL arguments / 3 or 4 quantisers") : JMHIP_ERR_ARG;
   const int n = c->me_n;
-  if (n <= 0 || !c->me_res_dev) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: no motion search results on the device (call jmhip_me_frame first)");
+  if (n <= 0 || !c->me_res_dev.ptr) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: no motion search results on the device (call jmhip_me_frame first)");
   if (c->cfg.yuv_format == JMHIP_YUV444) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_frame: 4:4:4 chroma goes through the luma path in JM (not built)");
   for (int k = 0; k < nquants; k++) {
     if (quants[k].qp < 0 || quants[k].qp > 87 || quants[k].max_val != 255 || quants[k].disthres < 0 || quants[k].disthres > 1)
@@ -316,7 +312,7 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
       }
     }
 
-  jmhip_mb_mode *modes_in_dev = nullptr, *modes_out_dev = (jmhip_mb_mode *)c->fr_modes;
+  jmhip_mb_mode *modes_in_dev = nullptr, *modes_out_dev = c->fr_modes.as<jmhip_mb_mode>();
   if (!modes && c->fr_from_slices) modes_in_dev = modes_out_dev + n;        // left there by jmhip_slice_to_frame
   if (modes) {
     modes_in_dev = modes_out_dev + n;
@@ -325,7 +321,7 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
   MbCoded *coded_dev = reinterpret_cast<MbCoded *>(modes_out_dev + 2 * (size_t)n);
   // the three quantisers are copied into a context-owned host block first: the caller's array is only borrowed for the call
   memcpy(c->fr_quant_host, quants, sizeof(jmhip_quant) * nquants);
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->fr_quant, c->fr_quant_host, sizeof(jmhip_quant) * nquants, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->fr_quant.ptr, c->fr_quant_host, sizeof(jmhip_quant) * nquants, hipMemcpyHostToDevice, c->stream));
   if (modes) JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // caller-owned mode array
 
   FrameDev F{};
@@ -333,17 +329,17 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
   F.yuv = c->cfg.yuv_format; F.shift_x = c->cg.shift_x; F.shift_y = c->cg.shift_y; F.mask_x = c->cg.mask_x; F.mask_y = c->cg.mask_y;
   F.sub_x = c->cg.sub_x; F.mb_cw = c->cg.mb_w; F.mb_ch = c->cg.mb_h;
   F.cur_y = c->cur_y; F.cur_u = c->cur_u; F.cur_v = c->cur_v;
-  const uint8_t *const *tab = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
+  const uint8_t *const *tab = c->ref_ptrs_dev.as<const uint8_t *const>();
   F.ref_sub = tab + 32; F.ref_cb = tab + 64; F.ref_cr = tab + 96;
-  F.rec_y = c->rec_y; F.rec_u = c->rec_u; F.rec_v = c->rec_v;
-  F.pred_y = c->keep_pred ? c->pred_y : nullptr; F.pred_u = c->keep_pred ? c->pred_u : nullptr; F.pred_v = c->keep_pred ? c->pred_v : nullptr;
+  F.rec_y = c->rec_y.as<uint8_t>(); F.rec_u = c->rec_u.as<uint8_t>(); F.rec_v = c->rec_v.as<uint8_t>();
+  F.pred_y = c->keep_pred ? c->pred_y.as<uint8_t>() : nullptr; F.pred_u = c->keep_pred ? c->pred_u.as<uint8_t>() : nullptr; F.pred_v = c->keep_pred ? c->pred_v.as<uint8_t>() : nullptr;
   F.fly = chroma_fly ? 1 : 0; F.mul_x = c->cg.mul_x; F.mul_y = c->cg.mul_y; F.pad_cx = c->cg.pad_x; F.pad_cy = c->cg.pad_y;
-  for (int k = 0; k < 8; k++) { F.ref_u[k] = k < (int)c->refs.size() ? c->refs[k].u : nullptr; F.ref_v[k] = k < (int)c->refs.size() ? c->refs[k].v : nullptr; }
-  F.blk_ref = c->fr_from_slices ? (const int8_t *)c->fr_blk_ref : nullptr;
+  for (int k = 0; k < 8; k++) { F.ref_u[k] = k < (int)c->refs.size() ? c->refs[k].u.as<uint8_t>() : nullptr; F.ref_v[k] = k < (int)c->refs.size() ? c->refs[k].v.as<uint8_t>() : nullptr; }
+  F.blk_ref = c->fr_from_slices ? c->fr_blk_ref.as<const int8_t>() : nullptr;
   F.bi = nullptr;
   if (c->fr_bi_n) {
     if (c->fr_bi_n != n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: jmhip_frame_bipred_set was given another number of macroblocks");
-    F.bi = (const jmhip_mb_bipred *)c->fr_bi;
+    F.bi = c->fr_bi.as<const jmhip_mb_bipred>();
     for (int a = 0; a < 4; a++) for (int q = 0; q < 3; q++) {
       F.bu1[a][q] = c->fr_bw.weight1[a][q]; F.bo1[a][q] = c->fr_bw.offset1[a][q];
       for (int b = 0; b < 4; b++) { F.bw0[a][b][q] = c->fr_bw.w0[a][b][q]; F.bw1[a][b][q] = c->fr_bw.w1[a][b][q]; }
@@ -360,15 +356,10 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
                quants[1].adapt_rnd_weight >= 0 && quants[1].adapt_rnd_weight < 32768 &&
                (!any_t8 || (quants[3].adapt_rnd_weight >= 0 && quants[3].adapt_rnd_weight < 32768));
   if (const char *e = getenv("JMHIP_FRAME_FUSED")) if (!strcmp(e, "0")) fused = false;
-  if (fused && any_t8 && c->fr_rec8_capacity < n) {
-    if (c->fr_rec8) JM_HIP_CHECK(c, hipFree(c->fr_rec8));
-    c->fr_rec8 = nullptr; c->fr_rec8_capacity = 0;
-    if (hipMalloc(&c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "8x8-transform side records");
-    c->fr_rec8_capacity = n;
-  }
+  if (fused && any_t8 && !c->fr_rec8.grow(sizeof(jmhip_mb_residual8) * (size_t)n)) return jm_fail(c, JMHIP_ERR_NOMEM, "8x8-transform side records");
   if (fused) {
     jm_stage_begin(c, JMHIP_STAGE_MC);
-    rc = jm_launch_frame_fused(c, &F, c->me_jobs_dev, c->me_res_dev, modes_in_dev, modes_out_dev, c->fr_quant, c->fr_rec, coded_dev, n, any_t8 ? c->fr_rec8 : nullptr);
+    rc = jm_launch_frame_fused(c, &F, c->me_jobs_dev.ptr, c->me_res_dev.ptr, modes_in_dev, modes_out_dev, c->fr_quant.ptr, c->fr_rec.ptr, coded_dev, n, any_t8 ? c->fr_rec8.ptr : nullptr);
     jm_stage_end(c, JMHIP_STAGE_MC);                  // (the TQ stage has no launch of its own here: its time reads 0)
     if (rc) return rc;
     c->fr_n = n; c->rec_valid = true; c->fr_fused = true; c->fr_fused422 = f422; c->fr_fused8 = any_t8; c->pred_valid = c->keep_pred;
@@ -376,17 +367,17 @@ extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, 
   }
   c->fr_fused = false; c->fr_fused422 = false; c->fr_fused8 = false; c->pred_valid = false;
   jm_stage_begin(c, JMHIP_STAGE_MC);
-  mc_kernel<<<jm_xcd_grid(n), 64, 0, c->stream>>>(F, (const jmhip_me_mb *)c->me_jobs_dev, (const jmhip_me_result *)c->me_res_dev, modes_in_dev, modes_out_dev,
-                                                  (jmhip_tq_job *)c->fr_jobs_y, (jmhip_tq_job *)c->fr_jobs_c, n);
+  mc_kernel<<<jm_xcd_grid(n), 64, 0, c->stream>>>(F, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_res_dev.as<const jmhip_me_result>(), modes_in_dev, modes_out_dev,
+                                                  c->fr_jobs_y.as<jmhip_tq_job>(), c->fr_jobs_c.as<jmhip_tq_job>(), n);
   jm_stage_end(c, JMHIP_STAGE_MC);
   JM_HIP_CHECK(c, hipGetLastError());
   jm_stage_begin(c, JMHIP_STAGE_TQ);
-  rc = jm_launch_tq(c, JMHIP_TQ_LUMA4x4 | JMHIP_TQ_SELECT, F.yuv, c->fr_jobs_y, c->fr_quant, c->fr_res_y, n);
-  if (!rc && any_t8) rc = jm_launch_tq(c, JMHIP_TQ_LUMA8x8 | JMHIP_TQ_SELECT, F.yuv, c->fr_jobs_y, c->fr_quant, c->fr_res_y, n);
-  if (!rc && F.yuv != JMHIP_YUV400) rc = jm_launch_tq(c, JMHIP_TQ_CHROMA, F.yuv, c->fr_jobs_c, c->fr_quant, c->fr_res_c, 2 * n);
+  rc = jm_launch_tq(c, JMHIP_TQ_LUMA4x4 | JMHIP_TQ_SELECT, F.yuv, c->fr_jobs_y.ptr, c->fr_quant.ptr, c->fr_res_y.ptr, n);
+  if (!rc && any_t8) rc = jm_launch_tq(c, JMHIP_TQ_LUMA8x8 | JMHIP_TQ_SELECT, F.yuv, c->fr_jobs_y.ptr, c->fr_quant.ptr, c->fr_res_y.ptr, n);
+  if (!rc && F.yuv != JMHIP_YUV400) rc = jm_launch_tq(c, JMHIP_TQ_CHROMA, F.yuv, c->fr_jobs_c.ptr, c->fr_quant.ptr, c->fr_res_c.ptr, 2 * n);
   if (!rc) {
-    finalize_kernel<<<jm_xcd_grid(n), 64, 0, c->stream>>>(F, (const jmhip_me_mb *)c->me_jobs_dev, (const jmhip_tq_job *)c->fr_jobs_y, (const jmhip_tq_result *)c->fr_res_y,
-                                                          (const jmhip_tq_job *)c->fr_jobs_c, (const jmhip_tq_result *)c->fr_res_c, coded_dev, n);
+    finalize_kernel<<<jm_xcd_grid(n), 64, 0, c->stream>>>(F, c->me_jobs_dev.as<const jmhip_me_mb>(), c->fr_jobs_y.as<const jmhip_tq_job>(), c->fr_res_y.as<const jmhip_tq_result>(),
+                                                          c->fr_jobs_c.as<const jmhip_tq_job>(), c->fr_res_c.as<const jmhip_tq_result>(), coded_dev, n);
     if (hipGetLastError() != hipSuccess) rc = jm_fail(c, JMHIP_ERR_DEVICE, "finalize_kernel launch");
   }
   jm_stage_end(c, JMHIP_STAGE_TQ);
@@ -406,25 +397,25 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
   if (c->fr_fused && (luma || (chroma && c->Wc))) {
     if (c->fr_fused422) {
       recs422.resize(n);
-      JM_HIP_CHECK(c, hipMemcpyAsync(recs422.data(), c->fr_rec, sizeof(jmhip_mb_residual422) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+      JM_HIP_CHECK(c, hipMemcpyAsync(recs422.data(), c->fr_rec.ptr, sizeof(jmhip_mb_residual422) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     } else {
       recs.resize(n);
-      JM_HIP_CHECK(c, hipMemcpyAsync(recs.data(), c->fr_rec, sizeof(JmMbRes) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+      JM_HIP_CHECK(c, hipMemcpyAsync(recs.data(), c->fr_rec.ptr, sizeof(JmMbRes) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     }
     if (c->fr_fused8 && luma) {
       recs8.resize(n);
-      JM_HIP_CHECK(c, hipMemcpyAsync(recs8.data(), c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+      JM_HIP_CHECK(c, hipMemcpyAsync(recs8.data(), c->fr_rec8.ptr, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     }
   } else {
-    if (luma) JM_HIP_CHECK(c, hipMemcpyAsync(luma, c->fr_res_y, sizeof(jmhip_tq_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (chroma && c->Wc) JM_HIP_CHECK(c, hipMemcpyAsync(chroma, c->fr_res_c, sizeof(jmhip_tq_result) * (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+    if (luma) JM_HIP_CHECK(c, hipMemcpyAsync(luma, c->fr_res_y.ptr, sizeof(jmhip_tq_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (chroma && c->Wc) JM_HIP_CHECK(c, hipMemcpyAsync(chroma, c->fr_res_c.ptr, sizeof(jmhip_tq_result) * (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
   }
-  if (modes_out) JM_HIP_CHECK(c, hipMemcpyAsync(modes_out, c->fr_modes, sizeof(jmhip_mb_mode) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (modes_out) JM_HIP_CHECK(c, hipMemcpyAsync(modes_out, c->fr_modes.ptr, sizeof(jmhip_mb_mode) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   std::vector<MbCoded> coded;
   if (cbp || cbp_blk) {
     coded.resize(n);
     // the coded array sits after the 2*n modes of the last call (n == fr_n)
-    const MbCoded *coded_dev = reinterpret_cast<const MbCoded *>((jmhip_mb_mode *)c->fr_modes + 2 * (size_t)c->fr_n);
+    const MbCoded *coded_dev = reinterpret_cast<const MbCoded *>(c->fr_modes.as<jmhip_mb_mode>() + 2 * (size_t)c->fr_n);
     JM_HIP_CHECK(c, hipMemcpyAsync(coded.data(), coded_dev, sizeof(MbCoded) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   }
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
@@ -490,7 +481,7 @@ extern "C" int jmhip_residual_records_download(jmhip_ctx *c, jmhip_mb_residual *
   if (c->fr_fused && c->fr_fused422) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage took the fused 4:2:2 kernel (use jmhip_residual_records422_download)");
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage did not take the fused 4:2:0 kernel (use jmhip_residual_download)");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec, sizeof(jmhip_mb_residual) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec.ptr, sizeof(jmhip_mb_residual) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -502,7 +493,7 @@ extern "C" int jmhip_residual_records422_download(jmhip_ctx *c, jmhip_mb_residua
   if (c->fr_fused && !c->fr_fused422) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage took the fused 4:2:0 kernel (use jmhip_residual_records_download)");
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage did not take the fused 4:2:2 kernel (use jmhip_residual_download)");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec, sizeof(jmhip_mb_residual422) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec.ptr, sizeof(jmhip_mb_residual422) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -514,7 +505,7 @@ extern "C" int jmhip_residual_records8_download(jmhip_ctx *c, jmhip_mb_residual8
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records8_download: the last frame stage did not take the fused 4:2:0 / 4:2:2 kernel (use jmhip_residual_download)");
   if (!c->fr_fused8) { memset(records, 0, sizeof(jmhip_mb_residual8) * (size_t)n); return JMHIP_OK; }     // no 8x8-transform macroblock
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec8, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(records, c->fr_rec8.ptr, sizeof(jmhip_mb_residual8) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -523,17 +514,7 @@ extern "C" int jmhip_frame_keep_prediction(jmhip_ctx *c, int on)
 {
   if (!c) return JMHIP_ERR_ARG;
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  if (on && !c->pred_y) {
-    bool ok = hipMalloc((void **)&c->pred_y, (size_t)c->W * c->H) == hipSuccess;
-    if (ok && c->Wc) ok = hipMalloc((void **)&c->pred_u, (size_t)c->Wc * c->Hc) == hipSuccess && hipMalloc((void **)&c->pred_v, (size_t)c->Wc * c->Hc) == hipSuccess;
-    if (!ok) {
-      if (c->pred_y) (void)hipFree(c->pred_y);
-      if (c->pred_u) (void)hipFree(c->pred_u);
-      if (c->pred_v) (void)hipFree(c->pred_v);
-      c->pred_y = c->pred_u = c->pred_v = nullptr;
-      return jm_fail(c, JMHIP_ERR_NOMEM, "prediction picture");
-    }
-  }
+  if (on && !jm_ensure_planes(c, c->pred_y, c->pred_u, c->pred_v)) return jm_fail(c, JMHIP_ERR_NOMEM, "prediction picture");
   c->keep_pred = on != 0;
   if (!on) c->pred_valid = false;
   return JMHIP_OK;
@@ -542,12 +523,12 @@ extern "C" int jmhip_frame_keep_prediction(jmhip_ctx *c, int on)
 extern "C" int jmhip_pred_download(jmhip_ctx *c, void *Y, void *U, void *V, int pel_bytes)
 {
   if (!c) return JMHIP_ERR_ARG;
-  if (!c->pred_y || !c->pred_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_pred_download: no prediction picture (jmhip_frame_keep_prediction before a fused 4:2:0 / 4:2:2 jmhip_residual_frame)");
-  int rc = Y ? jm_download_planes(c, c->pred_y, (size_t)c->W * c->H, Y, pel_bytes) : JMHIP_OK;
+  if (!c->pred_y.ptr || !c->pred_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_pred_download: no prediction picture (jmhip_frame_keep_prediction before a fused 4:2:0 / 4:2:2 jmhip_residual_frame)");
+  int rc = Y ? jm_download_planes(c, c->pred_y.as<uint8_t>(), c->pred_y.bytes, Y, pel_bytes) : JMHIP_OK;
   if (rc) return rc;
   if (c->Wc && U && V) {
-    if ((rc = jm_download_planes(c, c->pred_u, (size_t)c->Wc * c->Hc, U, pel_bytes))) return rc;
-    if ((rc = jm_download_planes(c, c->pred_v, (size_t)c->Wc * c->Hc, V, pel_bytes))) return rc;
+    if ((rc = jm_download_planes(c, c->pred_u.as<uint8_t>(), c->pred_u.bytes, U, pel_bytes))) return rc;
+    if ((rc = jm_download_planes(c, c->pred_v.as<uint8_t>(), c->pred_v.bytes, V, pel_bytes))) return rc;
   }
   return JMHIP_OK;
 }
@@ -562,14 +543,14 @@ extern "C" int jmhip_recon_to_ref(jmhip_ctx *c, int ref)
 {
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
-  if (!c->rec_y || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_to_ref: no recon picture yet");
+  if (!c->rec_y.ptr || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_to_ref: no recon picture yet");
   RefSlot &r = c->refs[ref];
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  std::swap(r.y, c->rec_y);
-  if (c->Wc) { std::swap(r.u, c->rec_u); std::swap(r.v, c->rec_v); }
-  if (c->ref_ptrs_dev) {
+  r.y.swap(c->rec_y);
+  if (c->Wc) { r.u.swap(c->rec_u); r.v.swap(c->rec_v); }
+  if (c->ref_ptrs_dev.ptr) {
     if (c->table_fix.idx >= 0 && c->table_fix.idx != ref) { int rc = jm_flush_table_fix(c); if (rc) return rc; }
-    c->table_fix.idx = ref; c->table_fix.ptr = r.y;
+    c->table_fix.idx = ref; c->table_fix.ptr = r.y.as<uint8_t>();
   }
   r.has_pic = true; r.has_luma_sub = false; r.has_cr_sub = false;
   // the recon planes now hold the slot's OLD picture: nothing may read them as "the reconstruction" until the next
@@ -580,8 +561,8 @@ extern "C" int jmhip_recon_to_ref(jmhip_ctx *c, int ref)
 
 int jm_flush_table_fix(jmhip_ctx *c)
 {
-  if (c->table_fix.idx < 0 || !c->ref_ptrs_dev) { c->table_fix.idx = -1; return JMHIP_OK; }
-  set_plane_pointer<<<1, 1, 0, c->stream>>>(reinterpret_cast<const uint8_t **>(c->ref_ptrs_dev), c->table_fix.idx, c->table_fix.ptr);
+  if (c->table_fix.idx < 0 || !c->ref_ptrs_dev.ptr) { c->table_fix.idx = -1; return JMHIP_OK; }
+  set_plane_pointer<<<1, 1, 0, c->stream>>>(c->ref_ptrs_dev.as<const uint8_t *>(), c->table_fix.idx, c->table_fix.ptr);
   c->table_fix.idx = -1;
   JM_HIP_CHECK(c, hipGetLastError());
   return JMHIP_OK;
@@ -590,14 +571,14 @@ int jm_flush_table_fix(jmhip_ctx *c)
 extern "C" int jmhip_recon_copy_band(jmhip_ctx *c, void *Y, void *U, void *V, int mb_row0, int mb_rows)
 {
   if (!c || !Y) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_copy_band: NULL destination") : JMHIP_ERR_ARG;
-  if (!c->rec_y || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_copy_band: no recon picture yet");
+  if (!c->rec_y.ptr || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_copy_band: no recon picture yet");
   if (mb_row0 < 0 || mb_rows <= 0 || mb_row0 + mb_rows > c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_copy_band: band outside the picture");
   const size_t y0 = (size_t)mb_row0 * 16 * c->W, yn = (size_t)mb_rows * 16 * c->W;
-  JM_HIP_CHECK(c, hipMemcpyAsync(Y, c->rec_y + y0, yn, hipMemcpyDeviceToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(Y, c->rec_y.as<uint8_t>() + y0, yn, hipMemcpyDeviceToDevice, c->stream));
   if (c->Wc && U && V) {
     const size_t c0 = (size_t)mb_row0 * c->cg.mb_h * c->Wc, cn = (size_t)mb_rows * c->cg.mb_h * c->Wc;
-    JM_HIP_CHECK(c, hipMemcpyAsync(U, c->rec_u + c0, cn, hipMemcpyDeviceToDevice, c->stream));
-    JM_HIP_CHECK(c, hipMemcpyAsync(V, c->rec_v + c0, cn, hipMemcpyDeviceToDevice, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyAsync(U, c->rec_u.as<uint8_t>() + c0, cn, hipMemcpyDeviceToDevice, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyAsync(V, c->rec_v.as<uint8_t>() + c0, cn, hipMemcpyDeviceToDevice, c->stream));
   }
   return JMHIP_OK;
 }
@@ -649,11 +630,11 @@ extern "C" size_t jmhip_band_chunk_bytes(jmhip_ctx *c, int band_rows)
 extern "C" int jmhip_recon_pack_band(jmhip_ctx *c, void *chunk, int rank, int band_rows)
 {
   if (!c || !chunk || rank < 0 || band_rows <= 0) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_pack_band: arguments") : JMHIP_ERR_ARG;
-  if (!c->rec_y || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_pack_band: no recon picture yet");
+  if (!c->rec_y.ptr || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_pack_band: no recon picture yet");
   if ((c->W & 3) || (c->Wc & 3)) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_recon_pack_band: plane widths must be multiples of 4");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   const BandGeom g = band_geom(c->W, c->Wc, c->H, c->Hc, c->Wc ? c->cg.mb_h : 0, band_rows);
-  band_copy_kernel<<<256, 256, 0, c->stream>>>(g, c->rec_y, c->rec_u, c->rec_v, (uint8_t *)chunk, rank, 1, 0);
+  band_copy_kernel<<<256, 256, 0, c->stream>>>(g, c->rec_y.as<uint8_t>(), c->rec_u.as<uint8_t>(), c->rec_v.as<uint8_t>(), (uint8_t *)chunk, rank, 1, 0);
   JM_HIP_CHECK(c, hipGetLastError());
   return JMHIP_OK;
 }
@@ -667,7 +648,7 @@ extern "C" int jmhip_ref_unpack_bands(jmhip_ctx *c, int ref, const void *chunks,
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   RefSlot &r = c->refs[ref];
   const BandGeom g = band_geom(c->W, c->Wc, c->H, c->Hc, c->Wc ? c->cg.mb_h : 0, band_rows);
-  band_copy_kernel<<<512, 256, 0, c->stream>>>(g, r.y, r.u, r.v, (uint8_t *)chunks, 0, world, 1);
+  band_copy_kernel<<<512, 256, 0, c->stream>>>(g, r.y.as<uint8_t>(), r.u.as<uint8_t>(), r.v.as<uint8_t>(), (uint8_t *)chunks, 0, world, 1);
   JM_HIP_CHECK(c, hipGetLastError());
   r.has_pic = true; r.has_luma_sub = false; r.has_cr_sub = false;
   return JMHIP_OK;
@@ -676,12 +657,12 @@ extern "C" int jmhip_ref_unpack_bands(jmhip_ctx *c, int ref, const void *chunks,
 extern "C" int jmhip_recon_download(jmhip_ctx *c, void *Y, void *U, void *V, int pel_bytes)
 {
   if (!c || !Y) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_download: NULL output") : JMHIP_ERR_ARG;
-  if (!c->rec_y || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_download: no recon picture yet");
-  int rc = jm_download_planes(c, c->rec_y, (size_t)c->W * c->H, Y, pel_bytes);
+  if (!c->rec_y.ptr || !c->rec_valid) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_recon_download: no recon picture yet");
+  int rc = jm_download_planes(c, c->rec_y.as<uint8_t>(), c->rec_y.bytes, Y, pel_bytes);
   if (rc) return rc;
   if (c->Wc && U && V) {
-    if ((rc = jm_download_planes(c, c->rec_u, (size_t)c->Wc * c->Hc, U, pel_bytes))) return rc;
-    if ((rc = jm_download_planes(c, c->rec_v, (size_t)c->Wc * c->Hc, V, pel_bytes))) return rc;
+    if ((rc = jm_download_planes(c, c->rec_u.as<uint8_t>(), c->rec_u.bytes, U, pel_bytes))) return rc;
+    if ((rc = jm_download_planes(c, c->rec_v.as<uint8_t>(), c->rec_v.bytes, V, pel_bytes))) return rc;
   }
   return JMHIP_OK;
 }

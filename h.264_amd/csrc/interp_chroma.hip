@@ -71,9 +71,9 @@ int jm_launch_interp_chroma(jmhip_ctx *c, int ref, int prow0, int prow1)
   if (g1 <= g0) return JMHIP_OK;
   dim3 grid((c->Wcp / 4 + 63) / 64, g1 - g0, 2), block(64, 4);
   switch (c->cfg.yuv_format) {
-  case JMHIP_YUV420: interp_chroma_kernel<8, 8, 1, 1><<<grid, block, 0, c->stream>>>(r.u, r.cr_sub[0], r.v, r.cr_sub[1], c->Wc, c->Hc, c->Wcp, c->Hcp, c->cg.pad_x, c->cg.pad_y, g0); break;
-  case JMHIP_YUV422: interp_chroma_kernel<8, 4, 1, 2><<<grid, block, 0, c->stream>>>(r.u, r.cr_sub[0], r.v, r.cr_sub[1], c->Wc, c->Hc, c->Wcp, c->Hcp, c->cg.pad_x, c->cg.pad_y, g0); break;
-  case JMHIP_YUV444: interp_chroma_kernel<4, 4, 2, 2><<<grid, block, 0, c->stream>>>(r.u, r.cr_sub[0], r.v, r.cr_sub[1], c->Wc, c->Hc, c->Wcp, c->Hcp, c->cg.pad_x, c->cg.pad_y, g0); break;
+  case JMHIP_YUV420: interp_chroma_kernel<8, 8, 1, 1><<<grid, block, 0, c->stream>>>(r.u.as<uint8_t>(), r.cr_sub[0].as<uint8_t>(), r.v.as<uint8_t>(), r.cr_sub[1].as<uint8_t>(), c->Wc, c->Hc, c->Wcp, c->Hcp, c->cg.pad_x, c->cg.pad_y, g0); break;
+  case JMHIP_YUV422: interp_chroma_kernel<8, 4, 1, 2><<<grid, block, 0, c->stream>>>(r.u.as<uint8_t>(), r.cr_sub[0].as<uint8_t>(), r.v.as<uint8_t>(), r.cr_sub[1].as<uint8_t>(), c->Wc, c->Hc, c->Wcp, c->Hcp, c->cg.pad_x, c->cg.pad_y, g0); break;
+  case JMHIP_YUV444: interp_chroma_kernel<4, 4, 2, 2><<<grid, block, 0, c->stream>>>(r.u.as<uint8_t>(), r.cr_sub[0].as<uint8_t>(), r.v.as<uint8_t>(), r.cr_sub[1].as<uint8_t>(), c->Wc, c->Hc, c->Wcp, c->Hcp, c->cg.pad_x, c->cg.pad_y, g0); break;
   default: return jm_fail(c, JMHIP_ERR_ARG, "interp_chroma: no chroma");
   }
   JM_HIP_CHECK(c, hipGetLastError());

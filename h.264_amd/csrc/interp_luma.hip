@@ -168,9 +168,9 @@ int jm_launch_interp_luma(jmhip_ctx *c, int ref, int prow0, int prow1)
   if (prow1 > prow0) { t0 = max(0, prow0) / TY; t1 = min(t1, (min(c->Hp, prow1) + TY - 1) / TY); }
   if (t1 <= t0) return JMHIP_OK;
   dim3 grid((c->Wp + TX - 1) / TX, t1 - t0), block(64, 4);
-  const bool fix = c->table_fix.idx >= 0 && c->ref_ptrs_dev;
-  interp_luma_kernel<<<grid, block, 0, c->stream>>>(r.y, r.luma_sub, c->W, c->H, c->Wp, c->Hp, t0,
-                                                   fix ? reinterpret_cast<const uint8_t **>(c->ref_ptrs_dev) : nullptr, c->table_fix.idx, c->table_fix.ptr);
+  const bool fix = c->table_fix.idx >= 0 && c->ref_ptrs_dev.ptr;
+  interp_luma_kernel<<<grid, block, 0, c->stream>>>(r.y.as<uint8_t>(), r.luma_sub.as<uint8_t>(), c->W, c->H, c->Wp, c->Hp, t0,
+                                                   fix ? c->ref_ptrs_dev.as<const uint8_t *>() : nullptr, c->table_fix.idx, c->table_fix.ptr);
   c->table_fix.idx = -1;
   JM_HIP_CHECK(c, hipGetLastError());
   return JMHIP_OK;

@@ -91,24 +91,21 @@ extern "C" int jmhip_ctx_create(const jmhip_config *cfg, jmhip_ctx **out)
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return JMHIP_ERR_DEVICE; }
   c->refs.resize(cfg->max_refs);
 
-  auto alloc = [&](uint8_t **p, size_t bytes) -> bool {
-    if (hipMalloc((void **)p, bytes) != hipSuccess) return false;
-    return hipMemsetAsync(*p, 0, bytes, c->stream) == hipSuccess;
-  };
+  auto alloc = [&](DevBuf &b, size_t bytes) -> bool { return b.alloc(bytes) && hipMemsetAsync(b.ptr, 0, b.bytes, c->stream) == hipSuccess; };
   bool ok = true;
   const size_t ysz = (size_t)c->W * c->H, csz = (size_t)c->Wc * c->Hc;
   for (auto &r : c->refs) {
-    ok = ok && alloc(&r.y, ysz);
-    ok = ok && alloc(&r.luma_sub, 16 * (size_t)c->Wp * c->Hp + 64);   // +64: unaligned row fetches read up to 11 bytes past a row start
+    ok = ok && alloc(r.y, ysz);
+    ok = ok && alloc(r.luma_sub, 16 * (size_t)c->Wp * c->Hp + 64);   // +64: unaligned row fetches read up to 11 bytes past a row start
     if (csz) {
-      ok = ok && alloc(&r.u, csz) && alloc(&r.v, csz);
+      ok = ok && alloc(r.u, csz) && alloc(r.v, csz);
       // zero-initialised like JM's calloc (memalloc.c:142): the last row/column are never written
-      for (int k = 0; k < 2; k++) ok = ok && alloc(&r.cr_sub[k], (size_t)c->cg.sub_x * c->cg.sub_y * c->Wcp * c->Hcp);
+      for (int k = 0; k < 2; k++) ok = ok && alloc(r.cr_sub[k], (size_t)c->cg.sub_x * c->cg.sub_y * c->Wcp * c->Hcp);
     }
   }
-  ok = ok && alloc(&c->cur_own[0], ysz);
-  if (csz) ok = ok && alloc(&c->cur_own[1], csz) && alloc(&c->cur_own[2], csz);
-  c->cur_y = c->cur_own[0]; c->cur_u = c->cur_own[1]; c->cur_v = c->cur_own[2];
+  ok = ok && alloc(c->cur_own[0], ysz);
+  if (csz) ok = ok && alloc(c->cur_own[1], csz) && alloc(c->cur_own[2], csz);
+  c->cur_y = c->cur_own[0].as<uint8_t>(); c->cur_u = c->cur_own[1].as<uint8_t>(); c->cur_v = c->cur_own[2].as<uint8_t>();
   if (!ok) { jmhip_ctx_destroy(c); return JMHIP_ERR_NOMEM; }
   if (hipStreamSynchronize(c->stream) != hipSuccess) { jmhip_ctx_destroy(c); return JMHIP_ERR_DEVICE; }
   *out = c;
@@ -120,25 +117,14 @@ extern "C" void jmhip_ctx_destroy(jmhip_ctx *c)
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto &r : c->refs) {
-    (void)hipFree(r.y); (void)hipFree(r.u); (void)hipFree(r.v); (void)hipFree(r.luma_sub);
-    (void)hipFree(r.cr_sub[0]); (void)hipFree(r.cr_sub[1]);
-  }
-  (void)hipFree(c->cur_own[0]); (void)hipFree(c->cur_own[1]); (void)hipFree(c->cur_own[2]);
   if (c->pin_host) (void)hipHostFree(c->pin_host);
   for (auto e : c->pin_evt) (void)hipEventDestroy(e);
-  (void)hipFree(c->stage_dev); (void)hipFree(c->me_jobs_dev); (void)hipFree(c->me_res_dev); (void)hipFree(c->ref_ptrs_dev); (void)hipFree(c->me_idx_dev); (void)hipFree(c->surf_dev); (void)hipFree(c->surf_jobs_dev);
-  (void)hipFree(c->bic_jobs_dev); (void)hipFree(c->bic_res_dev);
-  (void)hipFree(c->bis_dev); (void)hipFree(c->bis_jobs_dev);
-  (void)hipFree(c->tq_jobs_dev); (void)hipFree(c->tq_res_dev); (void)hipFree(c->tq_quant_dev);
-  (void)hipFree(c->fr_bi); (void)hipFree(c->fr_rec); (void)hipFree(c->fr_rec8); (void)hipFree(c->fr_blk_ref); (void)hipFree(c->fr_jobs_y); (void)hipFree(c->fr_jobs_c); (void)hipFree(c->fr_res_y); (void)hipFree(c->fr_res_c);
-  jm_slice_state_free(c);
-  jm_xslice_free(c);
-  (void)hipFree(c->dbk_dev); (void)hipFree(c->dbr_dev); (void)hipFree(c->fr_quant); (void)hipFree(c->fr_modes); (void)hipFree(c->rec_y); (void)hipFree(c->pred_y); (void)hipFree(c->pred_u); (void)hipFree(c->pred_v); (void)hipFree(c->rec_u); (void)hipFree(c->rec_v);
   for (auto &p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto e : c->evt_pool) (void)hipEventDestroy(e);
+  jm_slice_state_free(c);
+  jm_xslice_free(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;                                            // every device buffer is a DevBuf member: freed here
 }
 
 // ---------------------------------------------------------------------------------------- timing
@@ -230,32 +216,26 @@ __global__ void widen_u8_kernel(const uint8_t *__restrict__ src, uint16_t *__res
 
 static int ensure_stage(jmhip_ctx *c, size_t bytes)
 {
-  if (c->stage_bytes >= bytes) return JMHIP_OK;
-  if (c->stage_dev) JM_HIP_CHECK(c, hipFree(c->stage_dev));
-  c->stage_dev = nullptr; c->stage_bytes = 0;
-  if (hipMalloc(&c->stage_dev, bytes) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "staging buffer");
-  c->stage_bytes = bytes;
-  return JMHIP_OK;
+  return c->stage_dev.grow(bytes) ? JMHIP_OK : jm_fail(c, JMHIP_ERR_NOMEM, "staging buffer");
+}
+
+// a picture of the context's size: all three planes or none (a failed chroma allocation must not leave a luma plane that later calls take
+// as "allocated" and launch on null chroma pointers)
+bool jm_ensure_planes(jmhip_ctx *c, DevBuf &y, DevBuf &u, DevBuf &v)
+{
+  if (y.ptr) return true;
+  const size_t csz = (size_t)c->Wc * c->Hc;
+  if (y.alloc((size_t)c->W * c->H) && (!csz || (u.alloc(csz) && v.alloc(csz)))) return true;
+  y = DevBuf(); u = DevBuf(); v = DevBuf();
+  return false;
+}
+
+int jm_ensure_recon(jmhip_ctx *c)
+{
+  return jm_ensure_planes(c, c->rec_y, c->rec_u, c->rec_v) ? JMHIP_OK : jm_fail(c, JMHIP_ERR_NOMEM, "recon picture");
 }
 
 // copy one plane (w x h samples) into a tightly packed 8-bit device plane
-// the recon picture: all three planes or none (a failed chroma allocation must not leave a luma plane that later calls take
-// as "allocated" and launch on null chroma pointers)
-int jm_ensure_recon(jmhip_ctx *c)
-{
-  if (c->rec_y && (!c->Wc || (c->rec_u && c->rec_v))) return JMHIP_OK;
-  bool ok = hipMalloc((void **)&c->rec_y, (size_t)c->W * c->H) == hipSuccess;
-  if (ok && c->Wc) ok = hipMalloc((void **)&c->rec_u, (size_t)c->Wc * c->Hc) == hipSuccess && hipMalloc((void **)&c->rec_v, (size_t)c->Wc * c->Hc) == hipSuccess;
-  if (!ok) {
-    if (c->rec_y) (void)hipFree(c->rec_y);
-    if (c->rec_u) (void)hipFree(c->rec_u);
-    if (c->rec_v) (void)hipFree(c->rec_v);
-    c->rec_y = c->rec_u = c->rec_v = nullptr;
-    return jm_fail(c, JMHIP_ERR_NOMEM, "recon picture");
-  }
-  return JMHIP_OK;
-}
-
 int jm_upload_plane(jmhip_ctx *c, uint8_t *dst, const void *src, int w, int h, int pel_bytes, int stride, int device_ptrs)
 {
   if (!src) return jm_fail(c, JMHIP_ERR_ARG, "NULL plane");
@@ -270,10 +250,10 @@ int jm_upload_plane(jmhip_ctx *c, uint8_t *dst, const void *src, int w, int h, i
   size_t bytes = (size_t)stride * h * 2;
   int rc = ensure_stage(c, bytes);
   if (rc) return rc;
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->stage_dev, src, bytes, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->stage_dev.ptr, src, bytes, hipMemcpyHostToDevice, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));    // the caller's buffer is only borrowed for the call
   dim3 grid((w + 255) / 256, h);
-  narrow_u16_kernel<<<grid, 256, 0, c->stream>>>((const uint16_t *)c->stage_dev, dst, w, h, stride);
+  narrow_u16_kernel<<<grid, 256, 0, c->stream>>>(c->stage_dev.as<const uint16_t>(), dst, w, h, stride);
   JM_HIP_CHECK(c, hipGetLastError());
   // the staging buffer is reused by the next plane: order is kept by the stream
   return JMHIP_OK;
@@ -286,11 +266,11 @@ extern "C" int jmhip_ref_upload(jmhip_ctx *c, int ref, const void *Y, const void
   if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   RefSlot &r = c->refs[ref];
-  int rc = jm_upload_plane(c, r.y, Y, c->W, c->H, pel_bytes, stride_y, device_ptrs);
+  int rc = jm_upload_plane(c, r.y.as<uint8_t>(), Y, c->W, c->H, pel_bytes, stride_y, device_ptrs);
   if (rc) return rc;
   if (c->Wc) {
-    if ((rc = jm_upload_plane(c, r.u, U, c->Wc, c->Hc, pel_bytes, stride_c, device_ptrs))) return rc;
-    if ((rc = jm_upload_plane(c, r.v, V, c->Wc, c->Hc, pel_bytes, stride_c, device_ptrs))) return rc;
+    if ((rc = jm_upload_plane(c, r.u.as<uint8_t>(), U, c->Wc, c->Hc, pel_bytes, stride_c, device_ptrs))) return rc;
+    if ((rc = jm_upload_plane(c, r.v.as<uint8_t>(), V, c->Wc, c->Hc, pel_bytes, stride_c, device_ptrs))) return rc;
   }
   r.has_pic = true; r.has_luma_sub = false; r.has_cr_sub = false;
   return JMHIP_OK;
@@ -301,7 +281,7 @@ extern "C" int jmhip_cur_upload(jmhip_ctx *c, const void *Y, const void *U, cons
 {
   if (!c) return JMHIP_ERR_ARG;
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  c->cur_y = c->cur_own[0]; c->cur_u = c->cur_own[1]; c->cur_v = c->cur_own[2];
+  c->cur_y = c->cur_own[0].as<uint8_t>(); c->cur_u = c->cur_own[1].as<uint8_t>(); c->cur_v = c->cur_own[2].as<uint8_t>();
   int rc = jm_upload_plane(c, c->cur_y, Y, c->W, c->H, pel_bytes, stride_y, device_ptrs);
   if (rc) return rc;
   if (c->Wc && U && V) {
@@ -317,9 +297,9 @@ extern "C" int jmhip_ref_planes_peek(jmhip_ctx *c, int ref, void **Y, void **U, 
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
   const RefSlot &r = c->refs[ref];
-  if (Y) *Y = r.y;
-  if (U) *U = r.u;
-  if (V) *V = r.v;
+  if (Y) *Y = r.y.ptr;
+  if (U) *U = r.u.ptr;
+  if (V) *V = r.v.ptr;
   if (pitch_y) *pitch_y = c->W;
   if (pitch_c) *pitch_c = c->Wc;
   return JMHIP_OK;
@@ -348,9 +328,9 @@ extern "C" int jmhip_ref_device_planes(jmhip_ctx *c, int ref, void **Y, void **U
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
   RefSlot &r = c->refs[ref];
-  if (Y) *Y = r.y;
-  if (U) *U = r.u;
-  if (V) *V = r.v;
+  if (Y) *Y = r.y.ptr;
+  if (U) *U = r.u.ptr;
+  if (V) *V = r.v.ptr;
   if (pitch_y) *pitch_y = c->W;
   if (pitch_c) *pitch_c = c->Wc;
   r.has_pic = true;          // the caller writes the planes itself (device-to-device exchange)
@@ -366,9 +346,9 @@ int jm_download_planes(jmhip_ctx *c, const uint8_t *src, size_t n, void *out, in
   } else if (pel_bytes == 2) {
     int rc = ensure_stage(c, n * 2);
     if (rc) return rc;
-    widen_u8_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(src, (uint16_t *)c->stage_dev, n);
+    widen_u8_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(src, c->stage_dev.as<uint16_t>(), n);
     JM_HIP_CHECK(c, hipGetLastError());
-    JM_HIP_CHECK(c, hipMemcpyAsync(out, c->stage_dev, n * 2, hipMemcpyDeviceToHost, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyAsync(out, c->stage_dev.ptr, n * 2, hipMemcpyDeviceToHost, c->stream));
   } else return jm_fail(c, JMHIP_ERR_ARG, "pel_bytes must be 1 or 2");
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
@@ -379,7 +359,7 @@ extern "C" int jmhip_ref_download_luma(jmhip_ctx *c, int ref, void *out, int pel
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
   if (!c->refs[ref].has_luma_sub) return jm_fail(c, JMHIP_ERR_ARG, "luma sub-pel planes not built (call jmhip_interp_luma)");
-  return jm_download_planes(c, c->refs[ref].luma_sub, 16 * (size_t)c->Wp * c->Hp, out, pel_bytes);
+  return jm_download_planes(c, c->refs[ref].luma_sub.as<uint8_t>(), 16 * (size_t)c->Wp * c->Hp, out, pel_bytes);
 }
 
 extern "C" int jmhip_ref_download_chroma(jmhip_ctx *c, int ref, int uv, void *out, int pel_bytes)
@@ -388,7 +368,7 @@ extern "C" int jmhip_ref_download_chroma(jmhip_ctx *c, int ref, int uv, void *ou
   if (ref < 0 || ref >= (int)c->refs.size() || uv < 0 || uv > 1) return jm_fail(c, JMHIP_ERR_ARG, "ref/uv out of range");
   if (!c->Wc) return jm_fail(c, JMHIP_ERR_ARG, "4:0:0 has no chroma");
   if (!c->refs[ref].has_cr_sub) return jm_fail(c, JMHIP_ERR_ARG, "chroma sub-pel planes not built (call jmhip_interp_chroma)");
-  return jm_download_planes(c, c->refs[ref].cr_sub[uv], (size_t)c->cg.sub_x * c->cg.sub_y * c->Wcp * c->Hcp, out, pel_bytes);
+  return jm_download_planes(c, c->refs[ref].cr_sub[uv].as<uint8_t>(), c->refs[ref].cr_sub[uv].bytes, out, pel_bytes);
 }
 
 // Planes to the caller's own row pointers (JM keeps every plane as an array of rows, imgpel **): each plane travels as packed bytes into a
@@ -448,7 +428,7 @@ extern "C" int jmhip_ref_download_luma_rows(jmhip_ctx *c, int ref, void *const *
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
   if (!c->refs[ref].has_luma_sub) return jm_fail(c, JMHIP_ERR_ARG, "luma sub-pel planes not built (call jmhip_interp_luma)");
-  return download_planes_rows(c, c->refs[ref].luma_sub, 16, c->Hp, c->Wp, rows, pel_bytes);
+  return download_planes_rows(c, c->refs[ref].luma_sub.as<uint8_t>(), 16, c->Hp, c->Wp, rows, pel_bytes);
 }
 
 extern "C" int jmhip_ref_download_chroma_rows(jmhip_ctx *c, int ref, int uv, void *const *rows, int pel_bytes)
@@ -457,7 +437,7 @@ extern "C" int jmhip_ref_download_chroma_rows(jmhip_ctx *c, int ref, int uv, voi
   if (ref < 0 || ref >= (int)c->refs.size() || uv < 0 || uv > 1) return jm_fail(c, JMHIP_ERR_ARG, "ref/uv out of range");
   if (!c->Wc) return jm_fail(c, JMHIP_ERR_ARG, "4:0:0 has no chroma");
   if (!c->refs[ref].has_cr_sub) return jm_fail(c, JMHIP_ERR_ARG, "chroma sub-pel planes not built (call jmhip_interp_chroma)");
-  return download_planes_rows(c, c->refs[ref].cr_sub[uv], c->cg.sub_x * c->cg.sub_y, c->Hcp, c->Wcp, rows, pel_bytes);
+  return download_planes_rows(c, c->refs[ref].cr_sub[uv].as<uint8_t>(), c->cg.sub_x * c->cg.sub_y, c->Hcp, c->Wcp, rows, pel_bytes);
 }
 
 extern "C" int jmhip_interp_luma(jmhip_ctx *c, int ref)

@@ -17,10 +17,29 @@ struct ChromaGeom {           // chroma_mc_setup, lencod/src/lencod.c:2851-2884
 // what the frame stage keeps per macroblock after thresholding (frame.hip finalize_kernel); read by deblock.hip
 struct JmMbCoded { int32_t cbp; int32_t pad; int64_t cbp_blk; };
 
+// One device allocation and its byte count, freed with its owner (host code only; move-only). Every device allocation of the library is one of
+// these: members of jmhip_ctx and RefSlot, members of the slice-search states (me_wave.hip, me_xslice.hip), or locals of the entries that
+// allocate per call. alloc() releases what it held first and leaves it empty when the allocation fails; grow() keeps a buffer that is already
+// large enough. bytes is the one record of a buffer's capacity. Not one of these: pinned host memory (pin_host here, h_flags in me_xslice.hip)
+// and the -DJMHIP_STAMPS debugging pointer of me_int.hip (static storage: a destructor would run after the HIP runtime has shut down).
+struct DevBuf {
+  void *ptr = nullptr; size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept { swap(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }      // (o's destructor frees what this one held)
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (ptr) (void)hipFree(ptr); }
+  bool alloc(size_t n) { DevBuf().swap(*this); if (hipMalloc(&ptr, n) != hipSuccess) { ptr = nullptr; return false; } bytes = n; return true; }
+  bool grow(size_t n) { return bytes >= n || alloc(n); }
+  template <class T> T *as() const { return static_cast<T *>(ptr); }
+  void swap(DevBuf &o) { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); }
+};
+
 struct RefSlot {
-  uint8_t *y = nullptr, *u = nullptr, *v = nullptr;   // integer-pel recon, pitch = W / Wc
-  uint8_t *luma_sub = nullptr;                        // [16][Hp][Wp]
-  uint8_t *cr_sub[2] = {nullptr, nullptr};            // [sub_y*sub_x][Hcp][Wcp]
+  DevBuf y, u, v;                                     // integer-pel recon, pitch = W / Wc
+  DevBuf luma_sub;                                    // [16][Hp][Wp]
+  DevBuf cr_sub[2];                                   // [sub_y*sub_x][Hcp][Wcp]
   bool has_pic = false, has_luma_sub = false, has_cr_sub = false;
 };
 
@@ -32,54 +51,55 @@ struct jmhip_ctx {
   int mbw = 0, mbh = 0;
   ChromaGeom cg{};
   std::vector<RefSlot> refs;
-  uint8_t *cur_y = nullptr, *cur_u = nullptr, *cur_v = nullptr;            // the active current picture (owned or bound)
-  uint8_t *cur_own[3] = {nullptr, nullptr, nullptr};                          // the context's own planes (jmhip_cur_upload target)
+  uint8_t *cur_y = nullptr, *cur_u = nullptr, *cur_v = nullptr;            // the active current picture: views of cur_own or of planes bound by jmhip_cur_bind
+  DevBuf cur_own[3];                                                          // the context's own planes (jmhip_cur_upload target)
   bool has_cur = false;
   // staging for 16-bit sample conversion
-  void *stage_dev = nullptr; size_t stage_bytes = 0;
+  DevBuf stage_dev;
   // page-locked host staging of the row-pointer downloads (jmhip_ref_download_*_rows) and one event per plane in flight
   uint8_t *pin_host = nullptr; size_t pin_bytes = 0;
   std::vector<hipEvent_t> pin_evt;
-  // ME job/result arrays
-  void *me_jobs_dev = nullptr; void *me_res_dev = nullptr; int me_capacity = 0; int me_n = 0;
+  // ME job/result arrays: one group, valid together for me_capacity macroblocks (set last; 0 while any member is missing)
+  DevBuf me_jobs_dev, me_res_dev; int me_capacity = 0; int me_n = 0;
   int me_max_uw = 0, me_max_uh = 0, me_last_mode = 0, me_last_R = 0, me_last_rdopt = 0, me_last_lvl[2] = {0, 0};
   unsigned long long me_last_mask = 0;
   bool me_last_metric_path = false;
   unsigned me_ref_mask = 0;
-  void *me_idx_dev = nullptr;                         // macroblock indices: fast-path list then generic list
+  DevBuf me_idx_dev;                                  // macroblock indices: fast-path list then generic list
   std::vector<int> me_fast_idx, me_gen_idx;                           // reference slots used by the last ME call
-  void *surf_dev = nullptr, *surf_jobs_dev = nullptr; size_t surf_cap = 0, surf_jobs_cap = 0;   // jmhip_distortion_surface
-  void *bic_jobs_dev = nullptr, *bic_res_dev = nullptr; size_t bic_cap = 0;                       // jmhip_bipred_chain: jobs / results, grown on demand
-  void *bis_dev = nullptr, *bis_jobs_dev = nullptr; size_t bis_cap = 0, bis_jobs_cap = 0;         // jmhip_bipred_surface: surfaces / jobs, grown on demand
-  void *ref_ptrs_dev = nullptr;                       // [0..31] integer recon, [32..63] quarter-pel plane stacks
+  DevBuf surf_dev, surf_jobs_dev;                     // jmhip_distortion_surface: surfaces / jobs, grown on demand
+  DevBuf bic_jobs_dev, bic_res_dev;                   // jmhip_bipred_chain: jobs / results, grown on demand
+  DevBuf bis_dev, bis_jobs_dev;                       // jmhip_bipred_surface: surfaces / jobs, grown on demand
+  DevBuf ref_ptrs_dev;                                // [0..31] integer recon, [32..63] quarter-pel plane stacks
   // jmhip_recon_to_ref swaps plane pointers; the one table entry that changes is written by the next kernel that can carry it
   // (interp_luma, which every pipeline launches next) instead of a launch of its own; jm_ensure_ref_table flushes it otherwise
   struct TableFix { int idx = -1; const uint8_t *ptr = nullptr; } table_fix;
-  // frame pipeline (MC -> residual -> TQ -> recon): per-MB luma job/result, 2 chroma jobs/results, recon picture
-  void *fr_jobs_y = nullptr, *fr_jobs_c = nullptr, *fr_res_y = nullptr, *fr_res_c = nullptr, *fr_quant = nullptr, *fr_modes = nullptr;
+  // frame pipeline (MC -> residual -> TQ -> recon): per-MB luma job/result, 2 chroma jobs/results, recon picture. fr_jobs_*, fr_res_*, fr_modes,
+  // fr_blk_ref and fr_rec are one group, valid together for fr_capacity macroblocks (set last; 0 while any member is missing); fr_quant holds
+  // four quantisers whatever the picture and is allocated with the group's first allocation
+  DevBuf fr_jobs_y, fr_jobs_c, fr_res_y, fr_res_c, fr_quant, fr_modes;
   int fr_capacity = 0, fr_n = 0;
-  void *fr_rec = nullptr;                             // fused frame stage: one JmMbRes (4:2:2: jmhip_mb_residual422) record per macroblock (frame_common.h)
+  DevBuf fr_rec;                                      // fused frame stage: one JmMbRes (4:2:2: jmhip_mb_residual422) record per macroblock (frame_common.h)
   bool fr_fused = false;                              // the last jmhip_residual_frame took the fused kernel: results live in fr_rec
   bool fr_fused422 = false;                           // ... its 4:2:2 form: the records are jmhip_mb_residual422
-  void *fr_rec8 = nullptr;                            // ... and one jmhip_mb_residual8 per macroblock when the picture has 8x8-transform macroblocks
-  int fr_rec8_capacity = 0;
+  DevBuf fr_rec8;                                     // ... and one jmhip_mb_residual8 per macroblock when the picture has 8x8-transform macroblocks
   bool fr_fused8 = false;                             // the last fused stage was the 8x8-transform instantiation: fr_rec8 holds its side records
-  void *fr_blk_ref = nullptr;                         // [n][4] reference slot per 8x8 block (frame stage fed from the slice search)
+  DevBuf fr_blk_ref;                                  // [n][4] reference slot per 8x8 block (frame stage fed from the slice search)
   bool fr_slices_t8 = false;                          // ... and some of them may carry the 8x8-transform flag (Transform8x8Mode in the slice search)
   bool fr_from_slices = false;                        // modes + per-block references of the frame stage were left on the device by jmhip_slice_to_frame
-  void *fr_bi = nullptr; int fr_bi_n = 0, fr_bi_capacity = 0; unsigned fr_bi_mask = 0;   // second list of B macroblocks (jmhip_frame_bipred_set), device array
+  DevBuf fr_bi; int fr_bi_n = 0; unsigned fr_bi_mask = 0;   // second list of B macroblocks (jmhip_frame_bipred_set), device array
   jmhip_frame_bw fr_bw{};
   jmhip_frame_wp fr_wp{};                             // explicit weighted prediction of the frame stage (enable = 0: off)
   jmhip_quant fr_quant_host[4];
-  uint8_t *rec_y = nullptr, *rec_u = nullptr, *rec_v = nullptr;
-  uint8_t *pred_y = nullptr, *pred_u = nullptr, *pred_v = nullptr;   // jmhip_frame_keep_prediction: the prediction picture of the last fused frame stage
+  DevBuf rec_y, rec_u, rec_v;                         // all three or none (jm_ensure_recon)
+  DevBuf pred_y, pred_u, pred_v;                      // jmhip_frame_keep_prediction: the prediction picture of the last fused frame stage
   bool keep_pred = false, pred_valid = false;
   bool rec_valid = false;                             // the recon planes hold a reconstruction (cleared by jmhip_recon_to_ref's plane swap)
   bool rec_has_pic = false;                           // recon planes loaded by jmhip_recon_upload
-  void *dbk_dev = nullptr; size_t dbk_cap = 0;        // deblocking: macroblock / block / edge arrays
-  void *dbr_dev = nullptr; size_t dbr_cap = 0; int dbk_sweeps = 0;   // deblocking, relaxation schedule: per-macroblock records, change flags, counters
+  DevBuf dbk_dev;                                     // deblocking: macroblock / block / edge arrays
+  DevBuf dbr_dev; int dbk_sweeps = 0;                 // deblocking, relaxation schedule: per-macroblock records, change flags, counters
   // TQ arrays
-  void *tq_jobs_dev = nullptr, *tq_res_dev = nullptr, *tq_quant_dev = nullptr; int tq_capacity = 0, tq_qcap = 0;
+  DevBuf tq_jobs_dev, tq_res_dev, tq_quant_dev;
   void *slice_state = nullptr;                         // me_wave.hip: the P-slice search state (field arrays, EPZS / UMHexagonS memories)
   void *xslice_state = nullptr;                        // me_xslice.hip: call records and work lists of the exhaustive searches' sweeps
   // timing
@@ -108,21 +128,6 @@ static inline int jm_fail(jmhip_ctx *ctx, int code, const char *msg)
   return code;
 }
 
-// One device allocation and its byte count, freed with its owner (host code only; move-only). alloc() releases what it held first and leaves
-// it empty when the allocation fails. The slice-search states (me_wave.hip, me_xslice.hip) keep their buffers in these.
-struct DevBuf {
-  void *ptr = nullptr; size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf &&o) noexcept { swap(o); }
-  DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }      // (o's destructor frees what this one held)
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (ptr) (void)hipFree(ptr); }
-  bool alloc(size_t n) { DevBuf().swap(*this); if (hipMalloc(&ptr, n) != hipSuccess) { ptr = nullptr; return false; } bytes = n; return true; }
-  template <class T> T *as() const { return static_cast<T *>(ptr); }
-  void swap(DevBuf &o) { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); }
-};
-
 // RAII-less stage timer: call begin before the launches of a stage and end after them.
 void jm_stage_begin(jmhip_ctx *ctx, int stage);
 void jm_stage_end(jmhip_ctx *ctx, int stage);
@@ -136,7 +141,8 @@ int jm_launch_interp_chroma(jmhip_ctx *ctx, int ref, int prow0 = 0, int prow1 = 
 constexpr int JMHIP_TQ_SELECT = 0x100;   // frame stage: each luma kernel takes only the macroblocks of its transform size
 int jm_launch_tq(jmhip_ctx *ctx, int kind, int yuv_format, const void *jobs, const void *quants, void *results, int n);
 int jm_ensure_ref_table(jmhip_ctx *ctx);
-int jm_ensure_recon(jmhip_ctx *ctx);                                                       // jmhip_ctx.hip: all three recon planes or none
+bool jm_ensure_planes(jmhip_ctx *ctx, DevBuf &y, DevBuf &u, DevBuf &v);                    // jmhip_ctx.hip: all three planes of a picture or none
+int jm_ensure_recon(jmhip_ctx *ctx);                                                       // ... the recon picture
 int jm_flush_table_fix(jmhip_ctx *ctx);
 void jm_slice_state_free(jmhip_ctx *ctx);
 void jm_xslice_free(jmhip_ctx *ctx);                                                       // me_xslice.hip

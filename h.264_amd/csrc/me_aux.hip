@@ -99,19 +99,16 @@ extern "C" int jmhip_distortion_batch(jmhip_ctx *c, const jmhip_dist_job *jobs, 
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_ensure_ref_table(c);
   if (rc) return rc;
-  void *dj = nullptr, *dout = nullptr;
-  if (hipMalloc(&dj, sizeof(jmhip_dist_job) * (size_t)n) != hipSuccess || hipMalloc(&dout, sizeof(int32_t) * (size_t)n) != hipSuccess) {
-    (void)hipFree(dj); return jm_fail(c, JMHIP_ERR_NOMEM, "distortion batch arrays");
-  }
+  DevBuf dj, dout;                                      // per call; freed on every way out
+  if (!dj.alloc(sizeof(jmhip_dist_job) * (size_t)n) || !dout.alloc(sizeof(int32_t) * (size_t)n)) return jm_fail(c, JMHIP_ERR_NOMEM, "distortion batch arrays");
   MeDev P{};
   P.W = c->W; P.H = c->H; P.Wp = c->Wp; P.Hp = c->Hp; P.cur = c->cur_y;
-  P.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  P.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
-  hipError_t e = hipMemcpyAsync(dj, jobs, sizeof(jmhip_dist_job) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) { distortion_kernel<<<(n + 63) / 64, 64, 0, c->stream>>>(P, (const jmhip_dist_job *)dj, n, (int32_t *)dout); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  P.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  P.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
+  hipError_t e = hipMemcpyAsync(dj.ptr, jobs, dj.bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) { distortion_kernel<<<(n + 63) / 64, 64, 0, c->stream>>>(P, dj.as<const jmhip_dist_job>(), n, dout.as<int32_t>()); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, dout.bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dj); (void)hipFree(dout);
   if (e != hipSuccess) { c->err = std::string("jmhip_distortion_batch: ") + hipGetErrorString(e); return JMHIP_ERR_DEVICE; }
   return JMHIP_OK;
 }
@@ -256,22 +253,16 @@ extern "C" int jmhip_distortion_surface(jmhip_ctx *c, int kind, const jmhip_surf
   const int pitch = (UW + 15 + 3 + 4) & ~3;
   const size_t lds = (size_t)pitch * (UW + 15) + 16;
   if (lds > 48 * 1024) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_distortion_surface: range too large for one LDS window");
-  if (c->surf_cap < bytes || c->surf_jobs_cap < (size_t)n) {
-    if (c->surf_dev) JM_HIP_CHECK(c, hipFree(c->surf_dev));
-    if (c->surf_jobs_dev) JM_HIP_CHECK(c, hipFree(c->surf_jobs_dev));
-    c->surf_dev = c->surf_jobs_dev = nullptr; c->surf_cap = 0; c->surf_jobs_cap = 0;
-    if (hipMalloc(&c->surf_dev, bytes) != hipSuccess || hipMalloc(&c->surf_jobs_dev, sizeof(jmhip_surface_job) * (size_t)n) != hipSuccess)
-      return jm_fail(c, JMHIP_ERR_NOMEM, "distortion surface arrays");
-    c->surf_cap = bytes; c->surf_jobs_cap = (size_t)n;
-  }
+  const size_t job_bytes = sizeof(jmhip_surface_job) * (size_t)n;
+  if (!c->surf_dev.grow(bytes) || !c->surf_jobs_dev.grow(job_bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "distortion surface arrays");
   MeDev P{};
   P.W = c->W; P.H = c->H; P.Wp = c->Wp; P.Hp = c->Hp; P.cur = c->cur_y;
-  P.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->surf_jobs_dev, jobs, sizeof(jmhip_surface_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  if (kind == JMHIP_SURFACE_SAD_ROWS) surface_kernel<JMHIP_SURFACE_SAD_ROWS><<<n, 256, lds, c->stream>>>(P, (const jmhip_surface_job *)c->surf_jobs_dev, (uint16_t *)c->surf_dev);
-  else surface_kernel<JMHIP_SURFACE_SATD_BLOCKS><<<n, 256, lds, c->stream>>>(P, (const jmhip_surface_job *)c->surf_jobs_dev, (uint16_t *)c->surf_dev);
+  P.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->surf_jobs_dev.ptr, jobs, job_bytes, hipMemcpyHostToDevice, c->stream));
+  if (kind == JMHIP_SURFACE_SAD_ROWS) surface_kernel<JMHIP_SURFACE_SAD_ROWS><<<n, 256, lds, c->stream>>>(P, c->surf_jobs_dev.as<const jmhip_surface_job>(), c->surf_dev.as<uint16_t>());
+  else surface_kernel<JMHIP_SURFACE_SATD_BLOCKS><<<n, 256, lds, c->stream>>>(P, c->surf_jobs_dev.as<const jmhip_surface_job>(), c->surf_dev.as<uint16_t>());
   JM_HIP_CHECK(c, hipGetLastError());
-  JM_HIP_CHECK(c, hipMemcpyAsync(out, c->surf_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(out, c->surf_dev.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -650,23 +641,20 @@ extern "C" int jmhip_bipred_search(jmhip_ctx *c, const jmhip_bipred_params *prm,
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_ensure_ref_table(c);
   if (rc) return rc;
-  void *dj = nullptr, *dr = nullptr;
-  if (hipMalloc(&dj, sizeof(jmhip_bipred_job) * (size_t)n) != hipSuccess || hipMalloc(&dr, sizeof(jmhip_bipred_result) * (size_t)n) != hipSuccess) {
-    (void)hipFree(dj); return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred arrays");
-  }
+  DevBuf dj, dr;                                        // per call; freed on every way out
+  if (!dj.alloc(sizeof(jmhip_bipred_job) * (size_t)n) || !dr.alloc(sizeof(jmhip_bipred_result) * (size_t)n)) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred arrays");
   BiDev B{};
   B.W = c->W; B.H = c->H; B.Wp = c->Wp; B.Hp = c->Hp; B.cur = c->cur_y;
   B.lam_f = prm->lambda[0]; B.lam_h = prm->lambda[1]; B.lam_q = prm->lambda[2]; B.t8x8 = prm->transform8x8_mode ? 1 : 0;
   B.wp = prm->apply_weights ? 1 : 0; B.w1 = prm->weight1; B.w2 = prm->weight2; B.off = prm->offset_bi; B.rnd = prm->wp_luma_round; B.den = prm->luma_log_weight_denom;
-  B.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  B.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
+  B.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  B.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
   const int UW = 2 * maxR + 1, pitch = (UW + 15 + 3 + 4) & ~3;
   const size_t lds = (size_t)pitch * (UW + 15) + 16;
-  hipError_t e = hipMemcpyAsync(dj, jobs, sizeof(jmhip_bipred_job) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) { bipred_kernel<<<n, 256, lds, c->stream>>>(B, (const jmhip_bipred_job *)dj, (jmhip_bipred_result *)dr); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipMemcpyAsync(results, dr, sizeof(jmhip_bipred_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  hipError_t e = hipMemcpyAsync(dj.ptr, jobs, dj.bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) { bipred_kernel<<<n, 256, lds, c->stream>>>(B, dj.as<const jmhip_bipred_job>(), dr.as<jmhip_bipred_result>()); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(results, dr.ptr, dr.bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dj); (void)hipFree(dr);
   if (e != hipSuccess) { c->err = std::string("jmhip_bipred_search: ") + hipGetErrorString(e); return JMHIP_ERR_DEVICE; }
   return JMHIP_OK;
 }
@@ -694,27 +682,21 @@ extern "C" int jmhip_bipred_chain(jmhip_ctx *c, const jmhip_bipred_chain_params 
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_ensure_ref_table(c);
   if (rc) return rc;
-  if (c->bic_cap < (size_t)n) {
-    if (c->bic_jobs_dev) JM_HIP_CHECK(c, hipFree(c->bic_jobs_dev));
-    if (c->bic_res_dev) JM_HIP_CHECK(c, hipFree(c->bic_res_dev));
-    c->bic_jobs_dev = c->bic_res_dev = nullptr; c->bic_cap = 0;
-    if (hipMalloc(&c->bic_jobs_dev, sizeof(jmhip_bipred_chain_job) * (size_t)n) != hipSuccess || hipMalloc(&c->bic_res_dev, sizeof(jmhip_bipred_chain_result) * (size_t)n) != hipSuccess)
-      return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred chain arrays");
-    c->bic_cap = (size_t)n;
-  }
+  const size_t job_bytes = sizeof(jmhip_bipred_chain_job) * (size_t)n, res_bytes = sizeof(jmhip_bipred_chain_result) * (size_t)n;
+  if (!c->bic_jobs_dev.grow(job_bytes) || !c->bic_res_dev.grow(res_bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred chain arrays");
   BiDev B{};
   B.W = c->W; B.H = c->H; B.Wp = c->Wp; B.Hp = c->Hp; B.cur = c->cur_y;
   B.lam_f = prm->lambda[0]; B.lam_h = prm->lambda[1]; B.lam_q = prm->lambda[2]; B.t8x8 = prm->transform8x8_mode ? 1 : 0;
   B.wp = prm->apply_weights ? 1 : 0; B.w1 = prm->weight_a; B.w2 = prm->weight_b; B.off = prm->offset_bi; B.rnd = prm->wp_luma_round; B.den = prm->luma_log_weight_denom;
-  B.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  B.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
+  B.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  B.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
   const BiChain C = {prm->refinements, prm->search_range, prm->subpel};
   const int UW = 2 * prm->search_range + 1, pitch = (UW + 15 + 3 + 4) & ~3;      // step 0 has the largest window
   const size_t lds = (size_t)pitch * (UW + 15) + 16;
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->bic_jobs_dev, jobs, sizeof(jmhip_bipred_chain_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  bipred_chain_kernel<<<n, 256, lds, c->stream>>>(B, C, (const jmhip_bipred_chain_job *)c->bic_jobs_dev, (jmhip_bipred_chain_result *)c->bic_res_dev);
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->bic_jobs_dev.ptr, jobs, job_bytes, hipMemcpyHostToDevice, c->stream));
+  bipred_chain_kernel<<<n, 256, lds, c->stream>>>(B, C, c->bic_jobs_dev.as<const jmhip_bipred_chain_job>(), c->bic_res_dev.as<jmhip_bipred_chain_result>());
   JM_HIP_CHECK(c, hipGetLastError());
-  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->bic_res_dev, sizeof(jmhip_bipred_chain_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->bic_res_dev.ptr, res_bytes, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -822,28 +804,19 @@ extern "C" int jmhip_bipred_surface(jmhip_ctx *c, int kind, const jmhip_bipred_s
   int rc = jm_ensure_ref_table(c);
   if (rc) return rc;
   const size_t bytes = (size_t)n * UW * UW * nv * sizeof(uint16_t);
-  if (c->bis_cap < bytes) {
-    if (c->bis_dev) JM_HIP_CHECK(c, hipFree(c->bis_dev));
-    c->bis_dev = nullptr; c->bis_cap = 0;
-    if (hipMalloc(&c->bis_dev, bytes) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred surface array");
-    c->bis_cap = bytes;
-  }
-  if (c->bis_jobs_cap < (size_t)n) {
-    if (c->bis_jobs_dev) JM_HIP_CHECK(c, hipFree(c->bis_jobs_dev));
-    c->bis_jobs_dev = nullptr; c->bis_jobs_cap = 0;
-    if (hipMalloc(&c->bis_jobs_dev, sizeof(jmhip_bipred_surface_job) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred surface jobs");
-    c->bis_jobs_cap = (size_t)n;
-  }
+  const size_t job_bytes = sizeof(jmhip_bipred_surface_job) * (size_t)n;
+  if (!c->bis_dev.grow(bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred surface array");
+  if (!c->bis_jobs_dev.grow(job_bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "bi-pred surface jobs");
   BiDev B{};
   B.W = c->W; B.H = c->H; B.Wp = c->Wp; B.Hp = c->Hp; B.cur = c->cur_y;
-  B.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->bis_jobs_dev, jobs, sizeof(jmhip_bipred_surface_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  B.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->bis_jobs_dev.ptr, jobs, job_bytes, hipMemcpyHostToDevice, c->stream));
   jm_stage_begin(c, JMHIP_STAGE_ME_INT);
-  if (kind == JMHIP_SURFACE_SAD_ROWS) bipred_surface_kernel<JMHIP_SURFACE_SAD_ROWS><<<n, 256, lds, c->stream>>>(B, (const jmhip_bipred_surface_job *)c->bis_jobs_dev, (uint16_t *)c->bis_dev);
-  else bipred_surface_kernel<JMHIP_SURFACE_SATD_BLOCKS><<<n, 256, lds, c->stream>>>(B, (const jmhip_bipred_surface_job *)c->bis_jobs_dev, (uint16_t *)c->bis_dev);
+  if (kind == JMHIP_SURFACE_SAD_ROWS) bipred_surface_kernel<JMHIP_SURFACE_SAD_ROWS><<<n, 256, lds, c->stream>>>(B, c->bis_jobs_dev.as<const jmhip_bipred_surface_job>(), c->bis_dev.as<uint16_t>());
+  else bipred_surface_kernel<JMHIP_SURFACE_SATD_BLOCKS><<<n, 256, lds, c->stream>>>(B, c->bis_jobs_dev.as<const jmhip_bipred_surface_job>(), c->bis_dev.as<uint16_t>());
   jm_stage_end(c, JMHIP_STAGE_ME_INT);
   JM_HIP_CHECK(c, hipGetLastError());
-  JM_HIP_CHECK(c, hipMemcpyAsync(out, c->bis_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(out, c->bis_dev.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
@@ -989,18 +962,15 @@ extern "C" int jmhip_pred_cost_batch(jmhip_ctx *c, const jmhip_predcost_job *job
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   int rc = jm_ensure_ref_table(c);
   if (rc) return rc;
-  void *dj = nullptr, *dout = nullptr;
-  if (hipMalloc(&dj, sizeof(jmhip_predcost_job) * (size_t)n) != hipSuccess || hipMalloc(&dout, sizeof(int32_t) * 2 * (size_t)n) != hipSuccess) {
-    (void)hipFree(dj); return jm_fail(c, JMHIP_ERR_NOMEM, "prediction-cost arrays");
-  }
+  DevBuf dj, dout;                                      // per call; freed on every way out
+  if (!dj.alloc(sizeof(jmhip_predcost_job) * (size_t)n) || !dout.alloc(sizeof(int32_t) * 2 * (size_t)n)) return jm_fail(c, JMHIP_ERR_NOMEM, "prediction-cost arrays");
   MeDev P{};
   P.W = c->W; P.H = c->H; P.Wp = c->Wp; P.Hp = c->Hp; P.cur = c->cur_y;
-  P.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
-  hipError_t e = hipMemcpyAsync(dj, jobs, sizeof(jmhip_predcost_job) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) { predcost_kernel<<<n, 64, 0, c->stream>>>(P, (const jmhip_predcost_job *)dj, n, metric, layout, (int32_t *)dout); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  P.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
+  hipError_t e = hipMemcpyAsync(dj.ptr, jobs, dj.bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) { predcost_kernel<<<n, 64, 0, c->stream>>>(P, dj.as<const jmhip_predcost_job>(), n, metric, layout, dout.as<int32_t>()); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, dout.bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dj); (void)hipFree(dout);
   if (e != hipSuccess) { c->err = std::string("jmhip_pred_cost_batch: ") + hipGetErrorString(e); return JMHIP_ERR_DEVICE; }
   return JMHIP_OK;
 }

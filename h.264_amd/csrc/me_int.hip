@@ -1424,13 +1424,13 @@ int ensure_tables(jmhip_ctx *c)
 // [64..95] Cb eighth-pel stacks, [96..127] Cr
 int jm_ensure_ref_table(jmhip_ctx *c)
 {
-  if (c->ref_ptrs_dev) return jm_flush_table_fix(c);
+  if (c->ref_ptrs_dev.ptr) return jm_flush_table_fix(c);
   std::vector<const uint8_t *> tab(128, nullptr);
   for (size_t i = 0; i < c->refs.size(); i++) {
-    tab[i] = c->refs[i].y; tab[32 + i] = c->refs[i].luma_sub; tab[64 + i] = c->refs[i].cr_sub[0]; tab[96 + i] = c->refs[i].cr_sub[1];
+    tab[i] = c->refs[i].y.as<uint8_t>(); tab[32 + i] = c->refs[i].luma_sub.as<uint8_t>(); tab[64 + i] = c->refs[i].cr_sub[0].as<uint8_t>(); tab[96 + i] = c->refs[i].cr_sub[1].as<uint8_t>();
   }
-  if (hipMalloc(&c->ref_ptrs_dev, sizeof(void *) * 128) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "reference pointer table");
-  JM_HIP_CHECK(c, hipMemcpy(c->ref_ptrs_dev, tab.data(), sizeof(void *) * 128, hipMemcpyHostToDevice));
+  if (!c->ref_ptrs_dev.alloc(sizeof(void *) * tab.size())) return jm_fail(c, JMHIP_ERR_NOMEM, "reference pointer table");
+  JM_HIP_CHECK(c, hipMemcpy(c->ref_ptrs_dev.ptr, tab.data(), c->ref_ptrs_dev.bytes, hipMemcpyHostToDevice));
   return JMHIP_OK;
 }
 
@@ -1503,14 +1503,15 @@ static void host_center(const jmhip_me_params *prm, int pmx, int pmy, int *cx, i
 int jm_me_arrays_ensure(jmhip_ctx *c, int n)
 {
   if (c->me_capacity >= n) return JMHIP_OK;
-  if (c->me_jobs_dev) JM_HIP_CHECK(c, hipFree(c->me_jobs_dev));
-  if (c->me_res_dev) JM_HIP_CHECK(c, hipFree(c->me_res_dev));
-  if (c->me_idx_dev) JM_HIP_CHECK(c, hipFree(c->me_idx_dev));
-  c->me_jobs_dev = c->me_res_dev = c->me_idx_dev = nullptr; c->me_capacity = 0; c->me_n = 0;
-  if (hipMalloc(&c->me_jobs_dev, sizeof(jmhip_me_mb) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "ME job array");
-  if (hipMalloc(&c->me_res_dev, sizeof(jmhip_me_result) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "ME result array");
-  if (hipMalloc(&c->me_idx_dev, sizeof(int) * (size_t)n * FAST_MAX_CENTRES) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "ME index array");
-  c->me_capacity = n;
+  c->me_capacity = 0; c->me_n = 0;
+  const struct { DevBuf &buf; size_t bytes; const char *what; } group[] = {
+    {c->me_jobs_dev, sizeof(jmhip_me_mb) * (size_t)n, "ME job array"},
+    {c->me_res_dev, sizeof(jmhip_me_result) * (size_t)n, "ME result array"},
+    {c->me_idx_dev, sizeof(int) * (size_t)n * FAST_MAX_CENTRES, "ME index array"}};
+  auto release = [&] { for (auto &g : group) g.buf = DevBuf(); };
+  release();                                            // all of the old group before any of the new one, so that peak memory is one group
+  for (auto &g : group) if (!g.buf.alloc(g.bytes)) { release(); return jm_fail(c, JMHIP_ERR_NOMEM, g.what); }
+  c->me_capacity = n;                                   // set last: the three are valid together or not at all
   return JMHIP_OK;
 }
 
@@ -1518,7 +1519,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
 {
   if (!c || !prm || n <= 0) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: NULL/empty arguments") : JMHIP_ERR_ARG;
   const bool resident = (mbs == nullptr);            // reuse the job array uploaded (and validated) by the previous call
-  if (resident && (n != c->me_n || !c->me_jobs_dev)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: mbs == NULL needs a previous call with the same n");
+  if (resident && (n != c->me_n || !c->me_jobs_dev.ptr)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_frame: mbs == NULL needs a previous call with the same n");
   if (prm->search_mode != JMHIP_SEARCH_FULL && prm->search_mode != JMHIP_SEARCH_FASTFULL)
     return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_me_frame: search_mode must be -1 (FullSearch) or 0 (FastFullSearch); EPZS/UMHex run on the host over jmhip_distortion_batch");
   const int R = prm->search_range;
@@ -1615,11 +1616,11 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
   if ((rc = jm_me_arrays_ensure(c, n))) return rc;
   if ((rc = jm_ensure_ref_table(c))) return rc;
   if (!resident) {
-    JM_HIP_CHECK(c, hipMemcpyAsync(c->me_jobs_dev, mbs, sizeof(jmhip_me_mb) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyAsync(c->me_jobs_dev.ptr, mbs, sizeof(jmhip_me_mb) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     // index lists of the two integer-search kernels: [0, nfast) fast, [nfast, n) generic
     std::vector<int> idx(c->me_fast_idx);
     idx.insert(idx.end(), c->me_gen_idx.begin(), c->me_gen_idx.end());
-    JM_HIP_CHECK(c, hipMemcpyAsync(c->me_idx_dev, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, c->stream));
+    JM_HIP_CHECK(c, hipMemcpyAsync(c->me_idx_dev.ptr, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, c->stream));
     JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));     // idx is a stack vector
   }
   c->me_n = n; c->me_ref_mask = ref_mask; c->me_max_uw = max_uw; c->me_max_uh = max_uh;
@@ -1639,8 +1640,8 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
   P.W = c->W; P.H = c->H; P.Wp = c->Wp; P.Hp = c->Hp;
   P.win_pitch = pitch; P.win_rows = rows;
   P.cur = c->cur_y;
-  P.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  P.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
+  P.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  P.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
 
   const int nfast = (int)c->me_fast_idx.size(), ngen = (int)c->me_gen_idx.size();
 #ifdef JMHIP_STAMPS
@@ -1651,7 +1652,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
 #endif
   if (metric_path) {                                    // integer and sub-pel stage in one kernel
     jm_stage_begin(c, JMHIP_STAGE_ME_INT);
-    rc = jm_launch_me_metric(c, &eff, P, (const jmhip_me_mb *)c->me_jobs_dev, (const int *)c->me_idx_dev, (jmhip_me_result *)c->me_res_dev, ngen, lds, 0);
+    rc = jm_launch_me_metric(c, &eff, P, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_idx_dev.as<const int>(), c->me_res_dev.as<jmhip_me_result>(), ngen, lds, 0);
     jm_stage_end(c, JMHIP_STAGE_ME_INT);
     JM_HIP_CHECK(c, hipGetLastError());
     return rc;
@@ -1683,13 +1684,13 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
       if (const char *e = getenv("JMHIP_ME_PERS_GRID")) { const int g = atoi(e) & ~7; if (g >= 8 && g < grid) grid = g; }     // tests: few workgroups, many items each
       if (grid > jm_xcd_grid(nfast)) grid = jm_xcd_grid(nfast);
       PF.win_pitch = ppitch; PF.win_copy_stride = nwp;
-      me_int_pers_kernel<<<grid, 256, wlds, c->stream>>>(PF, (const jmhip_me_mb *)c->me_jobs_dev, (const int *)c->me_idx_dev, (jmhip_me_result *)c->me_res_dev, nfast);
+      me_int_pers_kernel<<<grid, 256, wlds, c->stream>>>(PF, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_idx_dev.as<const int>(), c->me_res_dev.as<jmhip_me_result>(), nfast);
     }
-    else if (use_pair) me_int_pair_kernel<false><<<jm_xcd_grid(nfast), 256, plds, c->stream>>>(PF, (const jmhip_me_mb *)c->me_jobs_dev, (const int *)c->me_idx_dev, (jmhip_me_result *)c->me_res_dev, nfast, nullptr, 0, nullptr);
-    else me_int_fast_kernel<<<jm_xcd_grid(nfast), 256, flds, c->stream>>>(PF, (const jmhip_me_mb *)c->me_jobs_dev, (const int *)c->me_idx_dev, (jmhip_me_result *)c->me_res_dev, nfast);
+    else if (use_pair) me_int_pair_kernel<false><<<jm_xcd_grid(nfast), 256, plds, c->stream>>>(PF, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_idx_dev.as<const int>(), c->me_res_dev.as<jmhip_me_result>(), nfast, nullptr, 0, nullptr);
+    else me_int_fast_kernel<<<jm_xcd_grid(nfast), 256, flds, c->stream>>>(PF, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_idx_dev.as<const int>(), c->me_res_dev.as<jmhip_me_result>(), nfast);
   }
   if (ngen)
-    me_int_kernel<<<jm_xcd_grid(ngen), 256, lds, c->stream>>>(P, (const jmhip_me_mb *)c->me_jobs_dev, (const int *)c->me_idx_dev + nfast, (jmhip_me_result *)c->me_res_dev, ngen);
+    me_int_kernel<<<jm_xcd_grid(ngen), 256, lds, c->stream>>>(P, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_idx_dev.as<const int>() + nfast, c->me_res_dev.as<jmhip_me_result>(), ngen);
   jm_stage_end(c, JMHIP_STAGE_ME_INT);
   JM_HIP_CHECK(c, hipGetLastError());
 #ifdef JMHIP_STAMPS
@@ -1709,7 +1710,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
 #endif
   if (P.subpel && metric_any) {                        // the refinement with the configured metrics, from the integer vectors and costs just left
     jm_stage_begin(c, JMHIP_STAGE_ME_SUB);
-    rc = jm_launch_me_metric(c, &eff, P, (const jmhip_me_mb *)c->me_jobs_dev, nullptr, (jmhip_me_result *)c->me_res_dev, n, 0, 1);
+    rc = jm_launch_me_metric(c, &eff, P, c->me_jobs_dev.as<const jmhip_me_mb>(), nullptr, c->me_res_dev.as<jmhip_me_result>(), n, 0, 1);
     jm_stage_end(c, JMHIP_STAGE_ME_SUB);
     JM_HIP_CHECK(c, hipGetLastError());
     return rc;
@@ -1720,7 +1721,7 @@ extern "C" int jmhip_me_frame_async(jmhip_ctx *c, const jmhip_me_params *prm, co
 #endif
     if ((rc = jm_me_sub_tables(c))) return rc;
     jm_stage_begin(c, JMHIP_STAGE_ME_SUB);
-    jm_launch_me_sub(c, P, (const jmhip_me_mb *)c->me_jobs_dev, (jmhip_me_result *)c->me_res_dev, n);
+    jm_launch_me_sub(c, P, c->me_jobs_dev.as<const jmhip_me_mb>(), c->me_res_dev.as<jmhip_me_result>(), n);
     jm_stage_end(c, JMHIP_STAGE_ME_SUB);
     JM_HIP_CHECK(c, hipGetLastError());
 #ifdef JMHIP_STAMPS
@@ -1747,7 +1748,7 @@ extern "C" int jmhip_me_results_download(jmhip_ctx *c, jmhip_me_result *results,
 {
   if (!c || !results || n <= 0) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_results_download: NULL/empty arguments") : JMHIP_ERR_ARG;
   if (n > c->me_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_me_results_download: more results requested than jobs enqueued");
-  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->me_res_dev, sizeof(jmhip_me_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->me_res_dev.ptr, sizeof(jmhip_me_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; i++)
     for (int p = 0; p < JMHIP_NPART; p++)

@@ -451,8 +451,8 @@ int jm_launch_me_metric(jmhip_ctx *c, const jmhip_me_params *prm, const MeDev &P
   M.wpad_c = (c->Wc - 1) + 2 * c->cg.pad_x - c->cg.mb_w; M.hpad_c = (c->Hc - 1) + 2 * c->cg.pad_y - c->cg.mb_h;      // image.c (size_x_cr_pad)
   M.csx = c->cg.shift_x - 2; M.csy = c->cg.shift_y - 2;
   M.cur_c[0] = c->cur_u; M.cur_c[1] = c->cur_v;
-  M.ref_c[0] = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 64;
-  M.ref_c[1] = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 96;
+  M.ref_c[0] = c->ref_ptrs_dev.as<const uint8_t *const>() + 64;
+  M.ref_c[1] = c->ref_ptrs_dev.as<const uint8_t *const>() + 96;
   M.wpc_round = prm->wp_chroma_round; M.wpc_denom = prm->wp_chroma_denom;
   for (int k = 0; k < 16; k++) for (int j = 0; j < 2; j++) { M.wpc_w[k][j] = prm->wp_weight_cr[k][j]; M.wpc_o[k][j] = prm->wp_offset_cr[k][j]; }
   if (M.chroma_int && !skip_int) {                      // chroma windows behind the luma window

@@ -310,10 +310,8 @@ extern "C" int jmhip_me_subpel(jmhip_ctx *c, const jmhip_me_params *prm, const j
     for (int i = 0; i < n; i++) ref_mask |= 1u << mbs[i].ref;
     if ((rc = jm_me_metric_check(c, prm, ref_mask, "jmhip_me_subpel"))) return rc;
   }
-  void *dj = nullptr, *dr = nullptr;
-  if (hipMalloc(&dj, sizeof(jmhip_me_mb) * (size_t)n) != hipSuccess || hipMalloc(&dr, sizeof(jmhip_me_result) * (size_t)n) != hipSuccess) {
-    (void)hipFree(dj); return jm_fail(c, JMHIP_ERR_NOMEM, "sub-pel arrays");
-  }
+  DevBuf dj, dr;                                        // per call; freed on every way out
+  if (!dj.alloc(sizeof(jmhip_me_mb) * (size_t)n) || !dr.alloc(sizeof(jmhip_me_result) * (size_t)n)) return jm_fail(c, JMHIP_ERR_NOMEM, "sub-pel arrays");
   MeDev P{};
   P.mode = prm->search_mode; P.R = prm->search_range; P.rdopt = prm->rdopt; P.is_b = prm->is_b_slice;
   P.lam_f = prm->lambda[0]; P.lam_h = prm->lambda[1]; P.lam_q = prm->lambda[2];
@@ -322,20 +320,19 @@ extern "C" int jmhip_me_subpel(jmhip_ctx *c, const jmhip_me_params *prm, const j
   for (int k = 0; k < 16; k++) { P.wp_w[k] = prm->wp_weight[k]; P.wp_o[k] = prm->wp_offset[k]; }
   P.mask = prm->partition_mask & ((1ull << JMHIP_NPART) - 1);
   P.W = c->W; P.H = c->H; P.Wp = c->Wp; P.Hp = c->Hp; P.cur = c->cur_y;
-  P.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  P.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
-  hipError_t e = hipMemcpyAsync(dj, mbs, sizeof(jmhip_me_mb) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dr, results, sizeof(jmhip_me_result) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  P.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  P.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
+  hipError_t e = hipMemcpyAsync(dj.ptr, mbs, dj.bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dr.ptr, results, dr.bytes, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
     jm_stage_begin(c, JMHIP_STAGE_ME_SUB);
-    if (metric_path) jm_launch_me_metric(c, prm, P, (const jmhip_me_mb *)dj, nullptr, (jmhip_me_result *)dr, n, 0, 1);
-    else jm_launch_me_sub(c, P, (const jmhip_me_mb *)dj, (jmhip_me_result *)dr, n);
+    if (metric_path) jm_launch_me_metric(c, prm, P, dj.as<const jmhip_me_mb>(), nullptr, dr.as<jmhip_me_result>(), n, 0, 1);
+    else jm_launch_me_sub(c, P, dj.as<const jmhip_me_mb>(), dr.as<jmhip_me_result>(), n);
     jm_stage_end(c, JMHIP_STAGE_ME_SUB);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(results, dr, sizeof(jmhip_me_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(results, dr.ptr, dr.bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dj); (void)hipFree(dr);
   if (e != hipSuccess) { c->err = std::string("jmhip_me_subpel: ") + hipGetErrorString(e); return JMHIP_ERR_DEVICE; }
   return JMHIP_OK;
 }

@@ -2561,7 +2561,7 @@ void SliceCall::fill_wave_dev()
   if (D.debug) fprintf(stderr, "jmhip: JMHIP_WAVE_DEBUG=%d is set: stages of the slice search are SKIPPED for timing experiments, its results are WRONG\n", D.debug);
   D.W = c->W; D.H = c->H; D.Wp = c->Wp; D.Hp = c->Hp; D.mbw = c->mbw; D.mbh = c->mbh; D.w4 = c->W / 4; D.h4 = c->H / 4;
   D.cur = c->cur_y;
-  D.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
+  D.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
   D.ref_idx = s->ref_idx.as<int8_t>(); D.mv = s->mv.as<short>(); D.prog = s->prog.as<int>(); D.flags = s->flags.as<int>();
   D.out = s->out.as<jmhip_mb_inter>(); D.ref8ts = s->ref8ts.as<int>();
   D.ep_dist = s->ep_dist.as<int>(); D.ep_motion = s->ep_motion.as<short>(); D.ep_col = s->ep_col.as<short>(); D.row0 = row_first;
@@ -2917,8 +2917,8 @@ static int slice_to_frame(jmhip_ctx *c, const int32_t *ref_slot, int num_refs, i
       if (dev >= 0 && dev < 64) part_uploaded[dev] = true;
     }
   }
-  slice_to_frame_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(s->out.as<jmhip_mb_inter>(), s->ref8ts.as<int>(), mb_first, n, c->mbw, sm, (jmhip_me_mb *)c->me_jobs_dev,
-                                                                (jmhip_me_result *)c->me_res_dev, (jmhip_mb_mode *)c->fr_modes + n, (int8_t *)c->fr_blk_ref, form);
+  slice_to_frame_kernel<<<(n + 127) / 128, 128, 0, c->stream>>>(s->out.as<jmhip_mb_inter>(), s->ref8ts.as<int>(), mb_first, n, c->mbw, sm, c->me_jobs_dev.as<jmhip_me_mb>(),
+                                                                c->me_res_dev.as<jmhip_me_result>(), c->fr_modes.as<jmhip_mb_mode>() + n, c->fr_blk_ref.as<int8_t>(), form);
   JM_HIP_CHECK(c, hipGetLastError());
   // the search-stage arrays now hold this picture; a resident re-run of jmhip_me_frame on them is meaningless and is refused (geometry check)
   c->me_n = n; c->me_ref_mask = mask; c->me_last_mode = 0x7fffffff; c->me_fast_idx.clear(); c->me_gen_idx.clear();

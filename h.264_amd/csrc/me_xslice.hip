@@ -889,8 +889,8 @@ int jm_xslice_run(jmhip_ctx *c, const jmhip_slice_params *prm, int8_t *ref_idx, 
   P.mask = (1ull << JMHIP_NPART) - 1;
   P.W = c->W; P.H = c->H; P.Wp = c->Wp; P.Hp = c->Hp;
   P.cur = c->cur_y;
-  P.ref_y = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev);
-  P.ref_sub = reinterpret_cast<const uint8_t *const *>(c->ref_ptrs_dev) + 32;
+  P.ref_y = c->ref_ptrs_dev.as<const uint8_t *const>();
+  P.ref_sub = c->ref_ptrs_dev.as<const uint8_t *const>() + 32;
   if ((rc = jm_me_pair_geometry(c, prm->search_range, &P, &plds))) return rc;
   JM_HIP_CHECK(c, hipMemcpyAsync(x->medev.ptr, &P, sizeof(MeDev), hipMemcpyHostToDevice, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (P is a stack object)

@@ -1423,28 +1423,18 @@ extern "C" int jmhip_tq_batch(jmhip_ctx *c, int kind, int yuv_format, const jmhi
     if (kind == JMHIP_TQ_CHROMA && (jobs[i].uv < 0 || jobs[i].uv > 1)) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_tq_batch: uv must be 0 or 1");
   }
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
-  if (c->tq_capacity < n) {
-    if (c->tq_jobs_dev) JM_HIP_CHECK(c, hipFree(c->tq_jobs_dev));
-    if (c->tq_res_dev) JM_HIP_CHECK(c, hipFree(c->tq_res_dev));
-    c->tq_jobs_dev = c->tq_res_dev = nullptr; c->tq_capacity = 0;
-    if (hipMalloc(&c->tq_jobs_dev, sizeof(jmhip_tq_job) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "TQ job array");
-    if (hipMalloc(&c->tq_res_dev, sizeof(jmhip_tq_result) * (size_t)n) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "TQ result array");
-    c->tq_capacity = n;
-  }
-  if (c->tq_qcap < nquants) {
-    if (c->tq_quant_dev) JM_HIP_CHECK(c, hipFree(c->tq_quant_dev));
-    c->tq_quant_dev = nullptr; c->tq_qcap = 0;
-    if (hipMalloc(&c->tq_quant_dev, sizeof(jmhip_quant) * (size_t)nquants) != hipSuccess) return jm_fail(c, JMHIP_ERR_NOMEM, "TQ quantiser array");
-    c->tq_qcap = nquants;
-  }
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->tq_jobs_dev, jobs, sizeof(jmhip_tq_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  JM_HIP_CHECK(c, hipMemcpyAsync(c->tq_quant_dev, quants, sizeof(jmhip_quant) * (size_t)nquants, hipMemcpyHostToDevice, c->stream));
-  JM_HIP_CHECK(c, hipMemsetAsync(c->tq_res_dev, 0, sizeof(jmhip_tq_result) * (size_t)n, c->stream));
+  const size_t job_bytes = sizeof(jmhip_tq_job) * (size_t)n, res_bytes = sizeof(jmhip_tq_result) * (size_t)n, quant_bytes = sizeof(jmhip_quant) * (size_t)nquants;
+  if (!c->tq_jobs_dev.grow(job_bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "TQ job array");
+  if (!c->tq_res_dev.grow(res_bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "TQ result array");
+  if (!c->tq_quant_dev.grow(quant_bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "TQ quantiser array");
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->tq_jobs_dev.ptr, jobs, job_bytes, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(c->tq_quant_dev.ptr, quants, quant_bytes, hipMemcpyHostToDevice, c->stream));
+  JM_HIP_CHECK(c, hipMemsetAsync(c->tq_res_dev.ptr, 0, res_bytes, c->stream));
   jm_stage_begin(c, JMHIP_STAGE_TQ);
-  int rc = jm_launch_tq(c, kind, yuv_format, c->tq_jobs_dev, c->tq_quant_dev, c->tq_res_dev, n);
+  int rc = jm_launch_tq(c, kind, yuv_format, c->tq_jobs_dev.ptr, c->tq_quant_dev.ptr, c->tq_res_dev.ptr, n);
   jm_stage_end(c, JMHIP_STAGE_TQ);
   if (rc) return rc;
-  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->tq_res_dev, sizeof(jmhip_tq_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  JM_HIP_CHECK(c, hipMemcpyAsync(results, c->tq_res_dev.ptr, res_bytes, hipMemcpyDeviceToHost, c->stream));
   JM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return JMHIP_OK;
 }
