@@ -191,27 +191,42 @@ def test_deblock_recon_from_the_frame_stage(pkg, idc, slice_rows):
 
 
 @pytest.mark.gpu
+def test_deblock_recon_from_a_mixed_slot_frame_stage(pkg):
+    """macroblocks on reference slots 0, 1 and 3: deblock.hip takes ref_id[0] from job.ref"""
+    recon_stage_case(pkg, 0, 0, 96, 64, 8, slots=(0, 1, 3))
+
+
+@pytest.mark.gpu
 def test_deblock_recon_2160p_eight_slices(pkg):
     """BASELINE config 4's layout at size: 3840x2160 cut into 8 slices of whole macroblock rows (17 rows each, the last 16), filter kept inside
     the slices (idc 2): search -> residual -> filter on the device, against the oracle's DeblockFrame on the same side information."""
     recon_stage_case(pkg, 2, 17, 3840, 2160, 16, spread=10)
 
 
-def recon_stage_case(pkg, idc, slice_rows, w, h, R, spread=6):
+def recon_stage_case(pkg, idc, slice_rows, w, h, R, spread=6, slots=(0,)):
     """jmhip_deblock_recon builds the filter's side information on the device from the results of me_frame + residual_frame.
-    Expected: the oracle's filter on the downloaded (unfiltered) reconstruction with the same information assembled on the host."""
+    Expected: the oracle's filter on the downloaded (unfiltered) reconstruction with the same information assembled on the host.
+    slots: the reference slots the macroblocks draw from (each uploaded and interpolated, with its own picture): ref_id = the job's slot, so
+    that edges between macroblocks of different slots are filtered with bS 1 whatever their vectors (loopFilter.c:334-337)."""
     from tests.test_frame import synth
     from tests.test_me import lambda_factors, make_mbs
     rng = np.random.default_rng(12)
     qp = 38
     cur, ref = synth(rng, w, h, 1)
-    ctx = pkg.Context(w, h, yuv_format=1, max_refs=1, search_range=R)
-    ctx.ref_upload(0, *ref)
-    ctx.interp_luma(0)
-    ctx.interp_chroma(0)
+    ctx = pkg.Context(w, h, yuv_format=1, max_refs=max(slots) + 1, search_range=R)
+    for k, slot in enumerate(slots):
+        # the further slots: the same scene under its own noise -- the vectors of neighbours on different slots then agree, and ref_id alone decides
+        pic = ref if k == 0 else tuple(np.clip(p.astype(int) + rng.integers(-3, 4, p.shape), 0, 255).astype(np.uint8) for p in ref)
+        ctx.ref_upload(slot, *pic)
+        ctx.interp_luma(slot)
+        ctx.interp_chroma(slot)
     ctx.cur_upload(*cur)
     mbw, mbh = w // 16, h // 16
     mbs_me = make_mbs(pkg, rng, mbw, mbh, spread, per_partition=(w < 1000))
+    if len(slots) > 1:
+        mbs_me["ref"] = rng.choice(slots, len(mbs_me))
+        mbs_me["ref_is_0"] = rng.integers(0, 2, len(mbs_me))
+        assert set(mbs_me["ref"]) == set(slots)
     prm = pkg.MeParams()
     prm.search_mode, prm.search_range, prm.rdopt = -1, R, 1
     prm.level_mv_min, prm.level_mv_max = -511, 511
@@ -242,6 +257,10 @@ def recon_stage_case(pkg, idc, slice_rows, w, h, R, spread=6):
             blks["ref_id"][k, 0] = int(job["ref"])
     want = oracle.deblock_frame(before[0], before[1], before[2], 1, mbs, blks)
     assert int((want[0] != before[0]).sum()) > 0
+    if len(slots) > 1:                                  # some edge has bS 1 only because the pictures differ: one picture for all would show
+        same_pic = blks.copy()
+        same_pic["ref_id"][:, 0] = 0
+        assert any(not np.array_equal(a, b) for a, b in zip(want, oracle.deblock_frame(before[0], before[1], before[2], 1, mbs, same_pic)))
     ctx.deblock_recon(qp, (qp - 2, qp - 3), disable_idc=idc, alpha_c0_offset=2, beta_offset=-2, slice_rows=slice_rows)
     after = ctx.recon_download()
     ctx.close()

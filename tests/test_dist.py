@@ -11,6 +11,22 @@ from tests.test_me import lambda_factors, make_mbs, make_pair
 pytestmark = pytest.mark.gpu
 
 
+def three_refs(rng, w, h):
+    """the current picture and three different reference pictures (slots 0, 1, 2): a job that names one must not be served from another"""
+    cur, ref = make_pair(rng, w, h, "shift")
+    refs = [ref, np.roll(make_pair(rng, w, h, "shift")[1], (2, -3), (0, 1)), make_pair(rng, w, h, "noise")[1]]
+    return cur, refs
+
+
+def open_three(pkg, cur, refs, w, h):
+    ctx = pkg.Context(w, h, yuv_format=0, max_refs=3, search_range=16)
+    for slot, ref in enumerate(refs):
+        ctx.ref_upload(slot, ref)
+        ctx.interp_luma(slot)
+    ctx.cur_upload(cur)
+    return ctx
+
+
 def oracle_dist(rp, cur16, job):
     L = oracle.lib()
     d = oracle.Dist()
@@ -34,11 +50,8 @@ def test_distortion_batch(pkg, umv):
     from h264_amd.jmhip import DIST_JOB_DTYPE
     rng = np.random.default_rng(11 + umv)
     w, h = 96, 64
-    cur, ref = make_pair(rng, w, h, "shift")
-    ctx = pkg.Context(w, h, yuv_format=0, max_refs=1, search_range=16)
-    ctx.ref_upload(0, ref)
-    ctx.interp_luma(0)
-    ctx.cur_upload(cur)
+    cur, refs = three_refs(rng, w, h)
+    ctx = open_three(pkg, cur, refs, w, h)
     n = 600
     jobs = np.zeros(n, dtype=DIST_JOB_DTYPE)
     sizes = [4, 8, 16]
@@ -63,11 +76,18 @@ def test_distortion_batch(pkg, umv):
         j["wp_round"] = (1 << (j["wp_denom"] - 1)) if j["wp_denom"] else 0
         j["weight"] = int(rng.integers(-64, 128))
         j["offset"] = int(rng.integers(-30, 31))
+        j["ref"] = int(rng.integers(3))
     got = ctx.distortion_batch(jobs)
     ctx.close()
-    rp = oracle.RefPic(ref, yuv_format=0)
+    rps = [oracle.RefPic(ref, yuv_format=0) for ref in refs]
     cur16 = cur.astype(np.uint16)
-    want = np.array([oracle_dist(rp, cur16, jobs[i]) for i in range(n)], np.int32)
+    want = np.array([oracle_dist(rps[int(jobs[i]["ref"])], cur16, jobs[i]) for i in range(n)], np.int32)
+    # a wrong slot must show: the unweighted half of the jobs sees three different pictures (a weighted job may not -- a negative weight
+    # with a small offset clips every sample to 0), so on each slot at least a third of the jobs answer differently from both other slots
+    others = [[oracle_dist(rps[k], cur16, jobs[i]) for k in range(3) if k != jobs[i]["ref"]] for i in range(n)]
+    tells = np.array([w not in o for w, o in zip(want, others)])
+    for slot in range(3):
+        assert tells[jobs["ref"] == slot].mean() >= 1 / 3, "slot %d: the pictures answer alike, a wrong slot would not show" % slot
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, (bad[:5], got[bad[:5]], want[bad[:5]], jobs[bad[:5]])
 
@@ -139,15 +159,13 @@ def test_distortion_surface(pkg, wp):
     from h264_amd.jmhip import SURFACE_JOB_DTYPE
     rng = np.random.default_rng(23)
     w, h, R = 64, 48, 4
-    cur, ref = make_pair(rng, w, h, "shift")
-    ctx = pkg.Context(w, h, yuv_format=0, max_refs=1, search_range=16)
-    ctx.ref_upload(0, ref)
-    ctx.interp_luma(0)
-    ctx.cur_upload(cur)
+    cur, refs = three_refs(rng, w, h)
+    ctx = open_three(pkg, cur, refs, w, h)
     jobs = np.zeros(3, dtype=SURFACE_JOB_DTYPE)
     # an inner macroblock, the top-left one pushed out of the picture, the bottom-right one pushed far out
     for i, (mx, my, cx, cy) in enumerate([(1, 1, 2, -1), (0, 0, -14, -9), (3, 2, 30, 25)]):
         jobs[i]["mb_x"], jobs[i]["mb_y"], jobs[i]["R"], jobs[i]["cx"], jobs[i]["cy"] = mx, my, R, cx, cy
+        jobs[i]["ref"] = (i + 1) % 3                  # the three jobs read three different slots
         if wp:
             jobs[i]["wp"], jobs[i]["weight"], jobs[i]["offset"], jobs[i]["wp_round"], jobs[i]["wp_denom"] = (1,) + wp
     sad = ctx.distortion_surface("sad_rows", jobs)
@@ -155,24 +173,24 @@ def test_distortion_surface(pkg, wp):
     ctx.close()
 
     L = oracle.lib()
-    rp = oracle.RefPic(ref, yuv_format=0)
+    rps = [oracle.RefPic(ref, yuv_format=0) for ref in refs]
     cur16 = cur.astype(np.uint16)
     proto = [C.POINTER(oracle.Dist), C.c_void_p] + [C.c_int] * 5
     L.jmo_sad.argtypes = proto
     L.jmo_satd.argtypes = proto
 
-    def dist(test8x8):
+    def dist(test8x8, rp):
         d = oracle.Dist()
         d.ref = C.pointer(rp.ref)
         d.umv, d.chroma_me, d.test8x8, d.max_val, d.max_val_uv = 1, 0, test8x8, 255, 255
         if wp:
             d.weight_luma, d.offset_luma, d.wp_luma_round, d.luma_log_weight_denom = wp
         return d
-    d4, d8 = dist(0), dist(1)
     L.jmo_sad_wp.argtypes = proto
     L.jmo_satd_wp.argtypes = proto
     f_sad, f_satd = (L.jmo_sad_wp, L.jmo_satd_wp) if wp else (L.jmo_sad, L.jmo_satd)
     for i, job in enumerate(jobs):
+        d4, d8 = dist(0, rps[int(job["ref"])]), dist(1, rps[int(job["ref"])])
         ox, oy = int(job["mb_x"]) * 16, int(job["mb_y"]) * 16
         for ay in range(2 * R + 1):
             for ax in range(2 * R + 1):
