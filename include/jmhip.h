@@ -255,7 +255,9 @@ int jmhip_distortion_batch(jmhip_ctx *ctx, const jmhip_dist_job *jobs, int n, in
  *                              computeSAD (src/me_distortion.c:364-375, row-wise exit :373)
  *   JMHIP_SURFACE_SATD_BLOCKS  20 uint16: [0..15] HadamardSAD4x4 of the 4x4 blocks (raster), [16..19] HadamardSAD8x8 of
  *                              the 8x8 blocks (computeSATD, :657-731, block-wise exit :690/:720)
- * Samples outside the picture follow UMV access (= per-sample clamp on the integer plane). */
+ * Samples outside the picture follow UMV access (= per-sample clamp on the integer plane).
+ * One R per call, 0..64: a mixed, negative or larger R is JMHIP_ERR_ARG (the range check comes first: the LDS limit lies beyond it and is
+ * never the answer here). |cx|, |cy| <= 4096. */
 enum { JMHIP_SURFACE_SAD_ROWS = 0, JMHIP_SURFACE_SATD_BLOCKS = 1 };
 typedef struct {
   int16_t mb_x, mb_y, ref, R; int16_t cx, cy;      /* centre (cx, cy) in pels                                         */
@@ -337,8 +339,9 @@ int jmhip_bipred_chain(jmhip_ctx *ctx, const jmhip_bipred_chain_params *prm, con
  * (= per-sample clamp on the integer plane). The weighted 8x8 entries are the Hadamard SADs of the straight 8x8 blocks, as the oracle's
  * jmo_bipred_satd forms them: computeBiPredSATD2's 8x8 branch reads its source one sample early per row (:1021 does not advance src_line),
  * which neither the oracle nor this entry restates -- a binding must not answer weighted 8x8-transform calls from this surface.
- * One R per call; R < 0 or mixed: JMHIP_ERR_ARG; an R whose window exceeds the LDS limit of jmhip_distortion_surface: JMHIP_ERR_UNSUPPORTED;
- * any other R above 64: JMHIP_ERR_ARG. |cx|, |cy|, |s_mv| <= 4096. */
+ * One R per call; R < 0 or mixed: JMHIP_ERR_ARG; an R whose window exceeds the 48 KiB of LDS a workgroup may take: JMHIP_ERR_UNSUPPORTED
+ * (this entry only: jmhip_distortion_surface answers JMHIP_ERR_ARG to every R above 64); any other R above 64: JMHIP_ERR_ARG.
+ * |cx|, |cy|, |s_mv| <= 4096. */
 typedef struct {
   int16_t mb_x, mb_y;
   int16_t ref1, ref2;       /* slots: FIXED block (listX[list][ref]) / SWEPT picture (listX[list^1][0]) */
