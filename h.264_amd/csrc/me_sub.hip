@@ -4,49 +4,62 @@
 #include "me_common.h"
 
 #ifndef SUB_NT
-#define SUB_NT 128    // threads per macroblock (measured at 1080p: 64 -> 0.078 ms, 128 -> 0.064, 256 -> 0.066)
+#define SUB_NT 128    // threads per macroblock (measured at 1080p before the leader records: 64 -> 0.078 ms, 128 -> 0.064, 256 -> 0.066);
+                      // a multiple of 64, at least 128: the leader pass takes one of the 112 items per lane
 #endif
 
 namespace {
 
-// One SATD sub-block of a partition. `mem`: all items (of any partition) on the same sub-block -- the seven block types
-// tile the macroblock with the same 4x4 (8x8) blocks --, ascending, -1 padded; `memp`: their partitions.
-struct SubItem { int8_t p, bx, by, bs; int8_t mem[7], memp[7]; int8_t pad[2]; };     // 20 bytes
-static_assert(sizeof(SubItem) == 20, "SubItem is staged to LDS as 5 dwords");
+// One SATD sub-block of a partition, packed for the leader pass (one item per lane, two registers). The seven block types tile the
+// macroblock with the same 4x4 (8x8) blocks: `memp` are the partitions of ALL items on this item's sub-block (itself included) in
+// ascending item order, 63 where there is none; the first `self` of them belong to earlier items.
+//   a: bits 0..29 memp[0..4] (6 bits each) | bit 30 clear (the leader record puts umv there) | bit 31 8x8 sub-block
+//   b: bits 0..11 memp[5..6] | 12..13 bx / 4 | 14..15 by / 4 | 16..21 partition | 22..24 self
+struct SubItem { uint32_t a, b; };
+constexpr int SUB_NOPART = 63;                      // s_pkey[63] holds a key nobody shares
 __constant__ SubItem c_sub4[112];                   // all partitions, 4x4 sub-blocks
 __constant__ SubItem c_sub8[64];                    // test8x8transform: 16 8x8 blocks (types <= 4) + 48 4x4 (types 5..7)
 SubItem h_sub4[112], h_sub8[64];
 
+__host__ __device__ __forceinline__ int sub_memp(uint32_t a, uint32_t b, int k) { return (int)(((k < 5 ? a >> (6 * k) : b >> (6 * (k - 5)))) & 63u); }
+
 void build_sub_tables()
 {
   build_part_table();
+  struct Blk { int p, bx, by, bs; };
+  static Blk t4[112], t8[64];
   int n4 = 0, n8 = 0;
-  auto put = [](SubItem *t, int &n, int p, int bx, int by, int bs) {
-    SubItem s{};
-    s.p = (int8_t)p; s.bx = (int8_t)bx; s.by = (int8_t)by; s.bs = (int8_t)bs;
-    t[n++] = s;
-  };
+  auto put = [](Blk *t, int &n, int p, int bx, int by, int bs) { t[n++] = Blk{p, bx, by, bs}; };
   for (int p = 0; p < JMHIP_NPART; p++) {
     const PartInfo &q = h_part[p];
     for (int y = 0; y < q.h4; y++) for (int x = 0; x < q.w4; x++)       // computeSATD order: y outer, x inner (:673-675)
-      put(h_sub4, n4, p, 4 * (q.x4 + x), 4 * (q.y4 + y), 4);
+      put(t4, n4, p, 4 * (q.x4 + x), 4 * (q.y4 + y), 4);
     if (q.bt <= 4) {
-      for (int y = 0; y < q.h4 / 2; y++) for (int x = 0; x < q.w4 / 2; x++) put(h_sub8, n8, p, 4 * q.x4 + 8 * x, 4 * q.y4 + 8 * y, 8);
+      for (int y = 0; y < q.h4 / 2; y++) for (int x = 0; x < q.w4 / 2; x++) put(t8, n8, p, 4 * q.x4 + 8 * x, 4 * q.y4 + 8 * y, 8);
     } else {
-      for (int y = 0; y < q.h4; y++) for (int x = 0; x < q.w4; x++) put(h_sub8, n8, p, 4 * (q.x4 + x), 4 * (q.y4 + y), 4);
+      for (int y = 0; y < q.h4; y++) for (int x = 0; x < q.w4; x++) put(t8, n8, p, 4 * (q.x4 + x), 4 * (q.y4 + y), 4);
     }
   }
-  auto link = [](SubItem *it, int n) {
+  auto pack = [](const Blk *it, int n, SubItem *out) {
     for (int i = 0; i < n; i++) {
-      int k = 0;
-      for (int j = 0; j < 7; j++) { it[i].mem[j] = -1; it[i].memp[j] = -1; }
+      int memp[7], k = 0, self = 0;
+      for (int j = 0; j < 7; j++) memp[j] = SUB_NOPART;
       for (int j = 0; j < n; j++)
-        if (it[j].bx == it[i].bx && it[j].by == it[i].by && it[j].bs == it[i].bs) { it[i].mem[k] = (int8_t)j; it[i].memp[k] = it[j].p; k++; }
+        if (it[j].bx == it[i].bx && it[j].by == it[i].by && it[j].bs == it[i].bs) { if (j < i) self++; memp[k++] = it[j].p; }
+      SubItem s{0, 0};
+      for (int j = 0; j < 5; j++) s.a |= (uint32_t)memp[j] << (6 * j);
+      if (it[i].bs == 8) s.a |= 0x80000000u;
+      s.b = (uint32_t)memp[5] | (uint32_t)memp[6] << 6 | (uint32_t)(it[i].bx >> 2) << 12 | (uint32_t)(it[i].by >> 2) << 14 | (uint32_t)it[i].p << 16 | (uint32_t)self << 22;
+      out[i] = s;
     }
   };
-  link(h_sub4, 112);
-  link(h_sub8, 64);
+  pack(t4, 112, h_sub4);
+  pack(t8, 64, h_sub8);
 }
+
+// c_s9x / c_s9y (me_common.h) + 1 as 2-bit fields: the position differs per lane, so the table read would be a vector load
+__device__ __forceinline__ int s9x(int pos) { return (int)((0x22215u >> (2 * pos)) & 3u) - 1; }
+__device__ __forceinline__ int s9y(int pos) { return (int)((0x29421u >> (2 * pos)) & 3u) - 1; }
 
 #ifdef JMHIP_STAMPS
 #define SSTAMP(k) do { if (P.stamps && blockIdx.x < 512 && threadIdx.x == 0) P.stamps[blockIdx.x * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -58,8 +71,13 @@ void build_sub_tables()
 // Per phase (half-pel: 9 positions, quarter-pel: 8): the SATD of a (4x4 | 8x8) sub-block at a candidate depends only on
 // the sub-block, the partition's current vector and its access method. The seven block types tile the macroblock with
 // the same sub-blocks, so wherever their vectors agree the value is shared: each distinct (sub-block, vector) is
-// evaluated once by a "leader" item (compacted list) that adds it to every partition it serves; the 9 candidates of
-// all partitions are then costed in parallel and JM's sequential strict-< scan becomes an atomic min on (cost, position).
+// evaluated once by a "leader" item that adds it to every partition it serves; the 9 candidates of all partitions are
+// then costed in parallel and JM's sequential strict-< scan becomes an atomic min on (cost, position).
+// Everything the evaluation needs of a leader is the same for all its candidates, so the leader pass (one item per lane,
+// all waves) resolves it once per phase into a 16-byte record: the sub-block's quarter-pel origin with the partition's
+// vector added, the access method, the block's place in the macroblock and the partitions it serves (the item's memp
+// fields and a 7-bit mask of those whose key equals the leader's). The records are compacted in ascending item order
+// (ballot per wave, the waves' counts through LDS); the evaluation loop reads records only.
 // The kernel is latency-bound (dependent LDS/global reads between barriers), hence the small register footprint
 // (T8 = false drops the 8x8 Hadamard path) for many resident workgroups.
 // LIST: the macroblocks are a device-resident list of job indices with a partition mask each, its length device-resident too (the slice
@@ -71,12 +89,13 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
   constexpr int NSUB = T8 ? 64 : 112;
   __shared__ __attribute__((aligned(16))) uint8_t s_cur[16][16];
   __shared__ __attribute__((aligned(16))) uint32_t s_c16[16][8];           // (x, x+1) sample pairs, biased (see satd4x4_packed)
-  __shared__ __attribute__((aligned(16))) uint32_t s_tab[NSUB * 5];         // the SubItem table
-  __shared__ int s_mvx[JMHIP_NPART], s_mvy[JMHIP_NPART], s_umv[JMHIP_NPART], s_px[JMHIP_NPART], s_py[JMHIP_NPART];
-  __shared__ unsigned s_pkey[JMHIP_NPART], s_best[JMHIP_NPART];
+  // leader records: x, y = quarter-pel origin + vector; z = SubItem::a | umv << 30; w = SubItem::b bits 0..15 | member mask << 16
+  __shared__ __attribute__((aligned(16))) uint4 s_rec[NSUB];
+  __shared__ int s_mvx[JMHIP_NPART], s_mvy[JMHIP_NPART], s_px[JMHIP_NPART], s_py[JMHIP_NPART];
+  __shared__ unsigned s_pkey[SUB_NOPART + 1], s_best[JMHIP_NPART];
   __shared__ int s_satd[JMHIP_NPART][9];
-  __shared__ short s_list[NSUB];
-  __shared__ int s_nlead;
+  __shared__ int s_wlead[NT / 64];                                         // leaders per wave
+  static_assert(NT % 64 == 0 && NT >= NSUB, "the leader pass takes one item per lane");
 
   const int tid = threadIdx.x;
   if (LIST) n_items = jm_shard_slots(n_dev);                          // sharded list (jmhip_internal.h): virtual slots
@@ -95,9 +114,8 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
   const int wpw = WP ? P.wp_w[job.ref] : 0, wpo = WP ? P.wp_o[job.ref] : 0;       // WP: weighted reference ME, a separate instantiation
   const size_t plane = (size_t)P.Wp * P.Hp;
   const int width_pad = P.Wp - 1 - 16, height_pad = P.Hp - 1 - 16;      // size_x_pad / size_y_pad, mbuffer.c:421-422
-  const SubItem *items = reinterpret_cast<const SubItem *>(s_tab);
+  const SubItem mine = tid < NSUB ? (T8 ? c_sub8 : c_sub4)[tid] : SubItem{0, 0};      // this lane's item of the leader pass, both phases
 
-  for (int d = tid; d < NSUB * 5; d += NT) s_tab[d] = reinterpret_cast<const uint32_t *>(T8 ? c_sub8 : c_sub4)[d];
   if (tid < 64) {
     const int r = tid >> 2, k = tid & 3;
     const uint32_t v = *reinterpret_cast<const uint32_t *>(P.cur + (size_t)(mby * 16 + r) * P.W + mbx * 16 + k * 4);
@@ -111,6 +129,7 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
     s_px[tid] = job.pred_mv[tid][0]; s_py[tid] = job.pred_mv[tid][1];
     s_mvx[tid] = o.mv_int[tid][0] << 2; s_mvy[tid] = o.mv_int[tid][1] << 2;      // mv-search.c:770-774
   }
+  if (tid == SUB_NOPART) s_pkey[SUB_NOPART] = 0x80000000u | SUB_NOPART;
   const int w16h = (P.lam_h * 16) >> 16;
   unsigned carried = 0xffffffffu;                    // lane p: running minimum as a (cost + bias) << 4 | position key
 
@@ -125,7 +144,6 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
       const int max_x4 = (P.W - bsx + 2 * JMHIP_PAD) << 2, max_y4 = (P.H - bsy + 2 * JMHIP_PAD) << 2;
       const int m = phase ? 0 : 1;                   // me_fullsearch.c:412-413 vs :468-469
       const int umv = !((p4x > m) && (p4x < max_x4 - m) && (p4y > m) && (p4y < max_y4 - m));
-      s_umv[tid] = umv;
       // identity of (vector, access method); an inactive partition gets a key nobody shares
       s_pkey[tid] = my_active ? ((unsigned)(mx + 16384) | ((unsigned)(my + 16384) << 15) | ((unsigned)umv << 30)) : (0x80000000u | (unsigned)tid);
       s_best[tid] = carried;                         // :785-788: INT_MAX before half-pel; the half-pel minimum is carried on
@@ -135,54 +153,56 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
     __syncthreads();
     SSTAMP(1 + 5 * phase);
 
-    // ---- leaders: wave 0 takes items lane and lane + 64; an item leads if no earlier item on its sub-block has its key
-    if (tid < 64) {
-      bool lead[2];
+    // ---- leaders: one item per lane; an item leads if no earlier item on its sub-block has its key. Its record is resolved here,
+    // once per phase: the members are the items on the sub-block whose partition has the leader's key (itself included)
+    bool lead = false;
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    if (tid < NSUB) {
+      const int p = (int)((mine.b >> 16) & 63u);
+      const unsigned key = s_pkey[p];
+      unsigned members = 0;
 #pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int it = tid + 64 * h;
-        lead[h] = false;
-        if (it < NSUB) {
-          const SubItem si = items[it];
-          const unsigned key = s_pkey[si.p];
-          bool l = !(key & 0x80000000u);
-#pragma unroll
-          for (int k = 0; k < 6; k++) if (si.mem[k] >= 0 && si.mem[k] < it && s_pkey[si.memp[k]] == key) l = false;
-          lead[h] = l;
-        }
-      }
-      const unsigned long long b0 = __ballot(lead[0]), b1 = __ballot(lead[1]);
-      const unsigned long long lt = (1ull << tid) - 1;
-      if (lead[0]) s_list[__popcll(b0 & lt)] = (short)tid;
-      if (lead[1]) s_list[__popcll(b0) + __popcll(b1 & lt)] = (short)(tid + 64);
-      if (tid == 0) s_nlead = __popcll(b0) + __popcll(b1);
+      for (int k = 0; k < 7; k++) members |= (unsigned)(s_pkey[sub_memp(mine.a, mine.b, k)] == key) << k;      // memp 63: a key nobody shares
+      const unsigned earlier = (1u << ((mine.b >> 22) & 7u)) - 1u;
+      lead = !(key & 0x80000000u) && !(members & earlier);
+      // quarter-pel coordinate of the sub-block origin incl. the pad offset (me_fullsearch.c:364-365, me_distortion.c:678)
+      rec.x = (unsigned)(((mbx * 16 + 4 * (int)((mine.b >> 12) & 3u) + JMHIP_PAD) << 2) + s_mvx[p]);
+      rec.y = (unsigned)(((mby * 16 + 4 * (int)((mine.b >> 14) & 3u) + JMHIP_PAD) << 2) + s_mvy[p]);
+      rec.z = mine.a | (key & 0x40000000u);            // the key's umv bit
+      rec.w = (mine.b & 0xffffu) | (members << 16);
     }
+    const unsigned long long ball = __ballot(lead);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if ((tid & 63) == 0) s_wlead[wave] = __popcll(ball);
+    __syncthreads();
+    int before = 0, K = 0;                             // leaders of the waves before this one, of all waves: wave-uniform
+#pragma unroll
+    for (int w = 0; w < NT / 64; w++) { const int n = __builtin_amdgcn_readfirstlane(s_wlead[w]); if (w < wave) before += n; K += n; }
+    if (lead) s_rec[before + __popcll(ball & ((1ull << (tid & 63)) - 1))] = rec;      // ascending item order across the waves
     __syncthreads();
     SSTAMP(2 + 5 * phase);
 
-    const int K = s_nlead, total = K * ncand;
+    const int total = K * ncand;
     // idx / K without the integer-division sequence: idx + 0.5 is never a multiple of K, so the float quotient stays at least 0.5 / K
     // (>= 0.0045) away from an integer while its error is below 1e-4 for idx < 1008
     const float rK = __builtin_amdgcn_rcpf((float)K);
     for (int idx = tid; idx < total; idx += NT) {
-      const int ci = (int)(((float)idx + 0.5f) * rK), it = s_list[idx - ci * K], cand = first + ci;     // adjacent lanes: adjacent sub-blocks, same plane
-      const SubItem si = items[it];
-      const int p = si.p;
-      // quarter-pel coordinate of the sub-block origin incl. the pad offset (me_fullsearch.c:364-365, me_distortion.c:678)
-      const int xq = ((mbx * 16 + si.bx + JMHIP_PAD) << 2) + s_mvx[p] + step * c_s9x[cand];
-      const int yq = ((mby * 16 + si.by + JMHIP_PAD) << 2) + s_mvy[p] + step * c_s9y[cand];
+      const int ci = (int)(((float)idx + 0.5f) * rK), cand = first + ci;
+      const uint4 ld = s_rec[idx - ci * K];                                 // adjacent lanes: adjacent sub-blocks, same plane
+      const int xq = (int)ld.x + step * s9x(cand), yq = (int)ld.y + step * s9y(cand);
+      const int bx = 4 * (int)((ld.w >> 12) & 3u), by = 4 * (int)((ld.w >> 14) & 3u);
       int xpos = xq >> 2, ypos = yq >> 2;
-      if (s_umv[p]) { xpos = clampi(xpos, 0, width_pad); ypos = clampi(ypos, 0, height_pad); }     // UMVLine4X, refbuf.c:37
+      if (ld.z & 0x40000000u) { xpos = clampi(xpos, 0, width_pad); ypos = clampi(ypos, 0, height_pad); }     // UMVLine4X, refbuf.c:37
       const uint8_t *rp = sub + (size_t)((yq & 3) * 4 + (xq & 3)) * plane + (size_t)ypos * P.Wp + xpos;
       int v;
-      if (!T8 || si.bs == 4) {
+      if (!T8 || !(ld.z & 0x80000000u)) {
         uint32_t ref[4], c01[4], c23[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           uint32_t hi;
           fetch_row(rp + (size_t)r * P.Wp, 4, &ref[r], &hi);
           if (WP) ref[r] = wp_apply4(ref[r], wpw, wpo, P.wp_round, P.wp_denom);             // computeSATDWP, me_distortion.c:734
-          const uint2 c = *reinterpret_cast<const uint2 *>(&s_c16[si.by + r][si.bx >> 1]);
+          const uint2 c = *reinterpret_cast<const uint2 *>(&s_c16[by + r][bx >> 1]);
           c01[r] = c.x; c23[r] = c.y;
         }
         v = satd4x4_packed(c01, c23, ref);
@@ -193,8 +213,8 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
           uint32_t lo, hi;
           fetch_row(rp + (size_t)r * P.Wp, 8, &lo, &hi);
           if (WP) { lo = wp_apply4(lo, wpw, wpo, P.wp_round, P.wp_denom); hi = wp_apply4(hi, wpw, wpo, P.wp_round, P.wp_denom); }
-          const uint32_t c0 = *reinterpret_cast<const uint32_t *>(&s_cur[si.by + r][si.bx]);
-          const uint32_t c1 = *reinterpret_cast<const uint32_t *>(&s_cur[si.by + r][si.bx + 4]);
+          const uint32_t c0 = *reinterpret_cast<const uint32_t *>(&s_cur[by + r][bx]);
+          const uint32_t c1 = *reinterpret_cast<const uint32_t *>(&s_cur[by + r][bx + 4]);
           int row[8];
 #pragma unroll
           for (int x = 0; x < 4; x++) { row[x] = (int)((c0 >> (8 * x)) & 255) - (int)((lo >> (8 * x)) & 255); row[4 + x] = (int)((c1 >> (8 * x)) & 255) - (int)((hi >> (8 * x)) & 255); }
@@ -214,10 +234,9 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
         }
         v = (s + 2) >> 2;                            // HadamardSAD8x8, me_distortion.c:342
       }
-      // the value serves every item on this sub-block whose partition has the same key (itself included)
-      const unsigned key = s_pkey[p];
+      // the value serves every member of the record (the leader included)
 #pragma unroll
-      for (int k = 0; k < 7; k++) if (si.mem[k] >= 0 && s_pkey[si.memp[k]] == key) atomicAdd(&s_satd[si.memp[k]][cand], v);
+      for (int k = 0; k < 7; k++) if (ld.w & (0x10000u << k)) atomicAdd(&s_satd[sub_memp(ld.z, ld.w, k)][cand], v);
     }
     __syncthreads();
     SSTAMP(3 + 5 * phase);
@@ -228,7 +247,7 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
       const int ci = idx / JMHIP_NPART, p = idx - ci * JMHIP_NPART, pos = first + ci;
       if (!((mask >> p) & 1)) continue;
       const int mvx = s_mvx[p], mvy = s_mvy[p];
-      const int cxm = mvx + step * c_s9x[pos], cym = mvy + step * c_s9y[pos];
+      const int cxm = mvx + step * s9x(pos), cym = mvy + step * s9y(pos);
       int mcost = mv_cost(lam, cxm - s_px[p], cym - s_py[p]) + s_satd[p][pos];
       // check_position0, me_fullsearch.c:361, :439-442 (half-pel position 0 only; the bias keeps the key unsigned)
       if (pos == 0 && !P.rdopt && !P.is_b && job.ref_is_0 && p == 0 && mvx == 0 && mvy == 0) mcost -= w16h;
@@ -239,7 +258,7 @@ __global__ __launch_bounds__(NT) void me_sub_kernel(MeDev P, const jmhip_me_mb *
     if (my_active) {
       const unsigned k = s_best[tid];
       const int best = (int)(k & 15u);
-      s_mvx[tid] += step * c_s9x[best]; s_mvy[tid] += step * c_s9y[best];
+      s_mvx[tid] += step * s9x(best); s_mvy[tid] += step * s9y(best);
       carried = (k & ~15u);                          // start_me_refinement_qp == 1: the minimum competes as position 0
     }
     SSTAMP(5 + 5 * phase);
