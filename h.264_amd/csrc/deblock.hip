@@ -915,6 +915,7 @@ extern "C" int jmhip_deblock_recon(jmhip_ctx *c, const jmhip_deblock_params *prm
 {
   if (!c || !prm) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: NULL argument") : JMHIP_ERR_ARG;
   if (!c->rec_y.ptr || c->fr_n <= 0 || c->fr_n != c->me_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: needs the macroblock list of the last jmhip_me_frame + jmhip_residual_frame");
+  if (c->fr_fused444) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_deblock_recon: after a 4:4:4 frame stage the strengths would have to read the coded bits of three planes (use jmhip_deblock_frame)");
   int row0 = prm->mb_row0, rows = prm->mb_rows;
   if (rows <= 0) { row0 = 0; rows = c->mbh; }
   if (row0 < 0 || row0 + rows > c->mbh) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_deblock_recon: row band outside the picture");

@@ -208,20 +208,23 @@ int jm_frame_buffers_ensure(jmhip_ctx *c, int n)
   c->fr_capacity = 0;
   // the group: every member with its size, and whether it is zeroed when (re)allocated -- the chroma job tiles are only partly written per frame
   // (mb_cr_size columns/rows) and the result records only where a kernel has work
+  // (a 4:4:4 context has no separate kernels: their job / result arrays keep a token size)
+  const bool f444 = c->cfg.yuv_format == JMHIP_YUV444;
+  const size_t nsep = f444 ? 1 : (size_t)n;
   const struct { DevBuf &buf; size_t bytes; bool zero; } group[] = {
-    {c->fr_jobs_y, sizeof(jmhip_tq_job) * (size_t)n, false},
-    {c->fr_jobs_c, sizeof(jmhip_tq_job) * (size_t)n * 2, true},
-    {c->fr_res_y, sizeof(jmhip_tq_result) * (size_t)n, true},
-    {c->fr_res_c, sizeof(jmhip_tq_result) * (size_t)n * 2, true},
+    {c->fr_jobs_y, sizeof(jmhip_tq_job) * nsep, false},
+    {c->fr_jobs_c, sizeof(jmhip_tq_job) * nsep * 2, true},
+    {c->fr_res_y, sizeof(jmhip_tq_result) * nsep, true},
+    {c->fr_res_c, sizeof(jmhip_tq_result) * nsep * 2, true},
     {c->fr_modes, (sizeof(jmhip_mb_mode) * 2 + sizeof(JmMbCoded)) * (size_t)n, false},
     {c->fr_blk_ref, 4 * (size_t)n, false},
-    {c->fr_rec, (c->cfg.yuv_format == JMHIP_YUV422 ? sizeof(jmhip_mb_residual422) : sizeof(JmMbRes)) * (size_t)n, false}};
+    {c->fr_rec, (f444 ? sizeof(jmhip_mb_residual444) : c->cfg.yuv_format == JMHIP_YUV422 ? sizeof(jmhip_mb_residual422) : sizeof(JmMbRes)) * (size_t)n, false}};
   auto release = [&] { for (auto &g : group) g.buf = DevBuf(); };
   release();                                            // all of the old group before any of the new one, so that peak memory is one group
   const int rc = [&]() -> int {
     for (auto &g : group) if (!g.buf.alloc(g.bytes)) return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage arrays");
     for (auto &g : group) if (g.zero) JM_HIP_CHECK(c, hipMemsetAsync(g.buf.ptr, 0, g.buf.bytes, c->stream));
-    if (!c->fr_quant.grow(sizeof(jmhip_quant) * 4)) return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage quantisers");
+    if (!c->fr_quant.grow(sizeof(jmhip_quant) * 6)) return jm_fail(c, JMHIP_ERR_NOMEM, "frame-stage quantisers");
     return JMHIP_OK;
   }();
   if (rc) release(); else c->fr_capacity = n;           // nothing half-made is left behind, and the capacity is set last
@@ -266,10 +269,10 @@ extern "C" int jmhip_residual_frame(jmhip_ctx *c, const jmhip_mb_mode *modes, co
 
 extern "C" int jmhip_residual_frame_q(jmhip_ctx *c, const jmhip_mb_mode *modes, const jmhip_quant *quants, int nquants)
 {
+  if (c && quants && c->cfg.yuv_format == JMHIP_YUV444) return jm_residual_frame444(c, modes, quants, nquants);      // Cb / Cr through the luma path: frame444.hip
   if (!c || !quants || (nquants != 3 && nquants != 4)) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: NULL arguments / 3 or 4 quantisers") : JMHIP_ERR_ARG;
   const int n = c->me_n;
   if (n <= 0 || !c->me_res_dev.ptr) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: no motion search results on the device (call jmhip_me_frame first)");
-  if (c->cfg.yuv_format == JMHIP_YUV444) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_frame: 4:4:4 chroma goes through the luma path in JM (not built)");
   for (int k = 0; k < nquants; k++) {
     if (quants[k].qp < 0 || quants[k].qp > 87 || quants[k].max_val != 255 || quants[k].disthres < 0 || quants[k].disthres > 1)
       return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_frame: quantiser out of range");
@@ -391,6 +394,11 @@ extern "C" int jmhip_residual_download(jmhip_ctx *c, jmhip_tq_result *luma, jmhi
 {
   if (!c) return JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_download: more macroblocks requested than processed");
+  if (c->fr_fused444) {                                  // three luma-shaped planes per macroblock: frame444.hip expands its own records
+    const int rc = jm_residual_download444(c, luma, chroma, n);
+    if (rc) return rc;
+    luma = nullptr; chroma = nullptr;                    // modes and coded bits below, as for every format
+  }
   std::vector<JmMbRes> recs;
   std::vector<jmhip_mb_residual422> recs422;
   std::vector<jmhip_mb_residual8> recs8;
@@ -478,6 +486,7 @@ extern "C" int jmhip_residual_records_download(jmhip_ctx *c, jmhip_mb_residual *
 {
   if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records_download: NULL") : JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records_download: more macroblocks requested than processed");
+  if (c->fr_fused444) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage was a 4:4:4 one (use jmhip_residual_records444_download)");
   if (c->fr_fused && c->fr_fused422) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage took the fused 4:2:2 kernel (use jmhip_residual_records422_download)");
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records_download: the last frame stage did not take the fused 4:2:0 kernel (use jmhip_residual_download)");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
@@ -490,6 +499,7 @@ extern "C" int jmhip_residual_records422_download(jmhip_ctx *c, jmhip_mb_residua
 {
   if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records422_download: NULL") : JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records422_download: more macroblocks requested than processed");
+  if (c->fr_fused444) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage was a 4:4:4 one (use jmhip_residual_records444_download)");
   if (c->fr_fused && !c->fr_fused422) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage took the fused 4:2:0 kernel (use jmhip_residual_records_download)");
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records422_download: the last frame stage did not take the fused 4:2:2 kernel (use jmhip_residual_download)");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
@@ -502,6 +512,7 @@ extern "C" int jmhip_residual_records8_download(jmhip_ctx *c, jmhip_mb_residual8
 {
   if (!c || !records) return c ? jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records8_download: NULL") : JMHIP_ERR_ARG;
   if (n <= 0 || n > c->fr_n) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_residual_records8_download: more macroblocks requested than processed");
+  if (c->fr_fused444) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records8_download: the last frame stage was a 4:4:4 one, three side records per macroblock (use jmhip_residual_records8_444_download)");
   if (!c->fr_fused) return jm_fail(c, JMHIP_ERR_UNSUPPORTED, "jmhip_residual_records8_download: the last frame stage did not take the fused 4:2:0 / 4:2:2 kernel (use jmhip_residual_download)");
   if (!c->fr_fused8) { memset(records, 0, sizeof(jmhip_mb_residual8) * (size_t)n); return JMHIP_OK; }     // no 8x8-transform macroblock
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
@@ -552,7 +563,7 @@ extern "C" int jmhip_recon_to_ref(jmhip_ctx *c, int ref)
     if (c->table_fix.idx >= 0 && c->table_fix.idx != ref) { int rc = jm_flush_table_fix(c); if (rc) return rc; }
     c->table_fix.idx = ref; c->table_fix.ptr = r.y.as<uint8_t>();
   }
-  r.has_pic = true; r.has_luma_sub = false; r.has_cr_sub = false;
+  r.has_pic = true; r.planes_stale();
   // the recon planes now hold the slot's OLD picture: nothing may read them as "the reconstruction" until the next
   // jmhip_residual_frame / jmhip_recon_upload has written a new one
   c->rec_valid = false;
@@ -650,7 +661,7 @@ extern "C" int jmhip_ref_unpack_bands(jmhip_ctx *c, int ref, const void *chunks,
   const BandGeom g = band_geom(c->W, c->Wc, c->H, c->Hc, c->Wc ? c->cg.mb_h : 0, band_rows);
   band_copy_kernel<<<512, 256, 0, c->stream>>>(g, r.y.as<uint8_t>(), r.u.as<uint8_t>(), r.v.as<uint8_t>(), (uint8_t *)chunks, 0, world, 1);
   JM_HIP_CHECK(c, hipGetLastError());
-  r.has_pic = true; r.has_luma_sub = false; r.has_cr_sub = false;
+  r.has_pic = true; r.planes_stale();
   return JMHIP_OK;
 }
 

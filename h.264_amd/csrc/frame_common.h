@@ -1,4 +1,5 @@
-// frame_common.h -- what the frame-stage translation units (frame.hip: MC / finalize / entry points, tq.hip: the fused 4:2:0 kernel) share.
+// frame_common.h -- what the frame-stage translation units (frame.hip: MC / finalize / entry points, tq.hip: the fused 4:2:0 / 4:2:2 kernel,
+// frame444.hip: the 4:4:4 stage) share.
 #pragma once
 #include "jmhip_internal.h"
 
@@ -90,6 +91,12 @@ __device__ __forceinline__ uint32_t luma_row4(const FrameDev &F, int slot, int x
 {
   const int xpos = clampi(xq >> 2, 0, F.Wp - 1 - 16) + ox4, ypos = clampi(yq >> 2, 0, F.Hp - 1 - 16) + oy4;   // UMVLine4X, refbuf.c:37
   return fetch4(F.ref_sub[slot] + (size_t)((yq & 3) * 4 + (xq & 3)) * F.Wp * F.Hp + (size_t)(ypos + rr) * F.Wp + xpos);
+}
+// the same from another table of quarter-pel plane stacks with the luma geometry: the 6-tap Cb / Cr planes of a 4:4:4 reference (frame444.hip)
+__device__ __forceinline__ uint32_t luma_row4(const FrameDev &F, const uint8_t *const *planes, int slot, int xq, int yq, int ox4, int oy4, int rr)
+{
+  const int xpos = clampi(xq >> 2, 0, F.Wp - 1 - 16) + ox4, ypos = clampi(yq >> 2, 0, F.Hp - 1 - 16) + oy4;
+  return fetch4(planes[slot] + (size_t)((yq & 3) * 4 + (xq & 3)) * F.Wp * F.Hp + (size_t)(ypos + rr) * F.Wp + xpos);
 }
 
 }  // namespace

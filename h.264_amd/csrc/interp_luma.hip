@@ -161,15 +161,21 @@ __global__ __launch_bounds__(256) void interp_luma_kernel(const uint8_t *__restr
 // rows [prow0, prow1) of the padded plane, widened to whole tiles; the full plane when prow1 <= prow0
 int jm_launch_interp_luma(jmhip_ctx *c, int ref, int prow0, int prow1)
 {
+  RefSlot &r = c->refs[ref];
+  return jm_launch_interp_luma_plane(c, r.y.as<uint8_t>(), r.luma_sub.as<uint8_t>(), prow0, prow1);
+}
+
+// the same kernel on any picture plane of the luma geometry (W x H in, [16][Hp][Wp] out): Cb / Cr of a 4:4:4 reference (jmhip_interp_chroma444)
+int jm_launch_interp_luma_plane(jmhip_ctx *c, const uint8_t *src, uint8_t *out, int prow0, int prow1)
+{
   // operand shapes the kernel assumes
   if ((c->Wp & 3) || (c->W & 3) || ((size_t)c->Wp * c->Hp) % 4) return jm_fail(c, JMHIP_ERR_ARG, "interp_luma: width must be a multiple of 4");
-  RefSlot &r = c->refs[ref];
   int t0 = 0, t1 = (c->Hp + TY - 1) / TY;
   if (prow1 > prow0) { t0 = max(0, prow0) / TY; t1 = min(t1, (min(c->Hp, prow1) + TY - 1) / TY); }
   if (t1 <= t0) return JMHIP_OK;
   dim3 grid((c->Wp + TX - 1) / TX, t1 - t0), block(64, 4);
   const bool fix = c->table_fix.idx >= 0 && c->ref_ptrs_dev.ptr;
-  interp_luma_kernel<<<grid, block, 0, c->stream>>>(r.y.as<uint8_t>(), r.luma_sub.as<uint8_t>(), c->W, c->H, c->Wp, c->Hp, t0,
+  interp_luma_kernel<<<grid, block, 0, c->stream>>>(src, out, c->W, c->H, c->Wp, c->Hp, t0,
                                                    fix ? c->ref_ptrs_dev.as<const uint8_t *>() : nullptr, c->table_fix.idx, c->table_fix.ptr);
   c->table_fix.idx = -1;
   JM_HIP_CHECK(c, hipGetLastError());

@@ -41,6 +41,7 @@ extern "C" int jmhip_sizeof(int which)
   case 22: return (int)sizeof(jmhip_mb_residual);
   case 23: return (int)sizeof(jmhip_mb_residual8);
   case 24: return (int)sizeof(jmhip_mb_residual422);
+  case 26: return (int)sizeof(jmhip_mb_residual444);      // (25 stays unassigned)
   case 30: return (int)sizeof(jmhip_bipred_chain_job);
   case 31: return (int)sizeof(jmhip_bipred_chain_params);
   case 32: return (int)sizeof(jmhip_bipred_chain_result);
@@ -272,7 +273,7 @@ extern "C" int jmhip_ref_upload(jmhip_ctx *c, int ref, const void *Y, const void
     if ((rc = jm_upload_plane(c, r.u.as<uint8_t>(), U, c->Wc, c->Hc, pel_bytes, stride_c, device_ptrs))) return rc;
     if ((rc = jm_upload_plane(c, r.v.as<uint8_t>(), V, c->Wc, c->Hc, pel_bytes, stride_c, device_ptrs))) return rc;
   }
-  r.has_pic = true; r.has_luma_sub = false; r.has_cr_sub = false;
+  r.has_pic = true; r.planes_stale();
   return JMHIP_OK;
 }
 
@@ -334,7 +335,7 @@ extern "C" int jmhip_ref_device_planes(jmhip_ctx *c, int ref, void **Y, void **U
   if (pitch_y) *pitch_y = c->W;
   if (pitch_c) *pitch_c = c->Wc;
   r.has_pic = true;          // the caller writes the planes itself (device-to-device exchange)
-  r.has_luma_sub = false; r.has_cr_sub = false;
+  r.planes_stale();
   return JMHIP_OK;
 }
 
@@ -367,7 +368,7 @@ extern "C" int jmhip_ref_download_chroma(jmhip_ctx *c, int ref, int uv, void *ou
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size() || uv < 0 || uv > 1) return jm_fail(c, JMHIP_ERR_ARG, "ref/uv out of range");
   if (!c->Wc) return jm_fail(c, JMHIP_ERR_ARG, "4:0:0 has no chroma");
-  if (!c->refs[ref].has_cr_sub) return jm_fail(c, JMHIP_ERR_ARG, "chroma sub-pel planes not built (call jmhip_interp_chroma)");
+  if (!c->refs[ref].has_cr_sub && !c->refs[ref].has_cr_luma6) return jm_fail(c, JMHIP_ERR_ARG, "chroma sub-pel planes not built (call jmhip_interp_chroma)");
   return jm_download_planes(c, c->refs[ref].cr_sub[uv].as<uint8_t>(), c->refs[ref].cr_sub[uv].bytes, out, pel_bytes);
 }
 
@@ -436,7 +437,7 @@ extern "C" int jmhip_ref_download_chroma_rows(jmhip_ctx *c, int ref, int uv, voi
   if (!c) return JMHIP_ERR_ARG;
   if (ref < 0 || ref >= (int)c->refs.size() || uv < 0 || uv > 1) return jm_fail(c, JMHIP_ERR_ARG, "ref/uv out of range");
   if (!c->Wc) return jm_fail(c, JMHIP_ERR_ARG, "4:0:0 has no chroma");
-  if (!c->refs[ref].has_cr_sub) return jm_fail(c, JMHIP_ERR_ARG, "chroma sub-pel planes not built (call jmhip_interp_chroma)");
+  if (!c->refs[ref].has_cr_sub && !c->refs[ref].has_cr_luma6) return jm_fail(c, JMHIP_ERR_ARG, "chroma sub-pel planes not built (call jmhip_interp_chroma)");
   return download_planes_rows(c, c->refs[ref].cr_sub[uv].as<uint8_t>(), c->cg.sub_x * c->cg.sub_y, c->Hcp, c->Wcp, rows, pel_bytes);
 }
 
@@ -457,6 +458,7 @@ extern "C" int jmhip_interp_luma(jmhip_ctx *c, int ref)
 // searches a band of macroblock rows needs the planes of that band +- (search range + predictor reach + block height) and
 // nothing else. The caller owns that margin; rows outside keep whatever an earlier call left there.
 static int interp_rows(jmhip_ctx *c, int ref, int row0, int row1, bool chroma);
+static int clear_luma6(jmhip_ctx *c, int ref);
 extern "C" int jmhip_interp_rows(jmhip_ctx *c, int ref, int row0, int row1) { return c ? interp_rows(c, ref, row0, row1, true) : JMHIP_ERR_ARG; }
 extern "C" int jmhip_interp_luma_rows(jmhip_ctx *c, int ref, int row0, int row1) { return c ? interp_rows(c, ref, row0, row1, false) : JMHIP_ERR_ARG; }
 
@@ -474,11 +476,25 @@ static int interp_rows(jmhip_ctx *c, int ref, int row0, int row1, bool chroma)
   if (c->Wc && chroma) {
     const int sy = c->cfg.yuv_format == JMHIP_YUV420 ? 1 : 0;       // luma rows -> chroma rows
     jm_stage_begin(c, JMHIP_STAGE_INTERP_CHROMA);
-    rc = jm_launch_interp_chroma(c, ref, (row0 >> sy) + c->cg.pad_y - 1, ((row1 + sy) >> sy) + c->cg.pad_y + 1);
+    rc = clear_luma6(c, ref);
+    if (!rc) rc = jm_launch_interp_chroma(c, ref, (row0 >> sy) + c->cg.pad_y - 1, ((row1 + sy) >> sy) + c->cg.pad_y + 1);
     jm_stage_end(c, JMHIP_STAGE_INTERP_CHROMA);
     if (rc) return rc;
     c->refs[ref].has_cr_sub = true;
   }
+  return JMHIP_OK;
+}
+
+// 4:4:4: the bilinear kernel never writes the last row of a plane (it keeps calloc's zero, interp_chroma.hip); after jmhip_interp_chroma444 that
+// row holds 6-tap samples, so it is zeroed again before the bilinear planes come back
+static int clear_luma6(jmhip_ctx *c, int ref)
+{
+  RefSlot &r = c->refs[ref];
+  if (!r.has_cr_luma6) return JMHIP_OK;
+  const size_t plane = (size_t)c->Wcp * c->Hcp;
+  for (int k = 0; k < 2; k++)
+    JM_HIP_CHECK(c, hipMemset2DAsync(r.cr_sub[k].as<uint8_t>() + plane - c->Wcp, plane, 0, (size_t)c->Wcp, (size_t)c->cg.sub_x * c->cg.sub_y, c->stream));
+  r.has_cr_luma6 = false;
   return JMHIP_OK;
 }
 
@@ -490,8 +506,31 @@ extern "C" int jmhip_interp_chroma(jmhip_ctx *c, int ref)
   if (!c->refs[ref].has_pic) return jm_fail(c, JMHIP_ERR_ARG, "reference picture not uploaded");
   JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
   jm_stage_begin(c, JMHIP_STAGE_INTERP_CHROMA);
-  int rc = jm_launch_interp_chroma(c, ref);
+  int rc = clear_luma6(c, ref);
+  if (!rc) rc = jm_launch_interp_chroma(c, ref);
   jm_stage_end(c, JMHIP_STAGE_INTERP_CHROMA);
   if (rc == JMHIP_OK) c->refs[ref].has_cr_sub = true;
+  return rc;
+}
+
+// 4:4:4: getSubImagesLuma under select_plane(PLANE_U / PLANE_V) (UnifiedOneForthPix, image.c:1647-1656): the luma kernel on the slot's Cb and Cr
+extern "C" int jmhip_interp_chroma444(jmhip_ctx *c, int ref)
+{
+  if (!c) return JMHIP_ERR_ARG;
+  if (c->cfg.yuv_format != JMHIP_YUV444) return jm_fail(c, JMHIP_ERR_ARG, "jmhip_interp_chroma444: 4:4:4 contexts only (other formats: jmhip_interp_chroma)");
+  if (ref < 0 || ref >= (int)c->refs.size()) return jm_fail(c, JMHIP_ERR_ARG, "ref slot out of range");
+  RefSlot &r = c->refs[ref];
+  if (!r.has_pic) return jm_fail(c, JMHIP_ERR_ARG, "reference picture not uploaded");
+  // the chroma plane buffers of a 4:4:4 slot have the luma planes' geometry: [16][Hp][Wp], pad 20
+  const size_t need = 16 * (size_t)c->Wp * c->Hp;
+  if (c->Wc != c->W || c->Hc != c->H || c->Wcp != c->Wp || c->Hcp != c->Hp || c->cg.sub_x * c->cg.sub_y != 16 || r.cr_sub[0].bytes != need || r.cr_sub[1].bytes != need)
+    return jm_fail(c, JMHIP_ERR_ARG, "jmhip_interp_chroma444: the slot's chroma planes do not have the luma geometry");
+  JM_HIP_CHECK(c, hipSetDevice(c->cfg.device));
+  r.has_cr_sub = false; r.has_cr_luma6 = false;
+  jm_stage_begin(c, JMHIP_STAGE_INTERP_CHROMA);
+  int rc = jm_launch_interp_luma_plane(c, r.u.as<uint8_t>(), r.cr_sub[0].as<uint8_t>());
+  if (!rc) rc = jm_launch_interp_luma_plane(c, r.v.as<uint8_t>(), r.cr_sub[1].as<uint8_t>());
+  jm_stage_end(c, JMHIP_STAGE_INTERP_CHROMA);
+  if (rc == JMHIP_OK) r.has_cr_luma6 = true;
   return rc;
 }

@@ -41,6 +41,8 @@ struct RefSlot {
   DevBuf luma_sub;                                    // [16][Hp][Wp]
   DevBuf cr_sub[2];                                   // [sub_y*sub_x][Hcp][Wcp]
   bool has_pic = false, has_luma_sub = false, has_cr_sub = false;
+  bool has_cr_luma6 = false;                          // 4:4:4: cr_sub holds the 6-tap planes of jmhip_interp_chroma444 (then has_cr_sub is false)
+  void planes_stale() { has_luma_sub = has_cr_sub = has_cr_luma6 = false; }      // the slot's picture changed
 };
 
 struct jmhip_ctx {
@@ -76,7 +78,7 @@ struct jmhip_ctx {
   struct TableFix { int idx = -1; const uint8_t *ptr = nullptr; } table_fix;
   // frame pipeline (MC -> residual -> TQ -> recon): per-MB luma job/result, 2 chroma jobs/results, recon picture. fr_jobs_*, fr_res_*, fr_modes,
   // fr_blk_ref and fr_rec are one group, valid together for fr_capacity macroblocks (set last; 0 while any member is missing); fr_quant holds
-  // four quantisers whatever the picture and is allocated with the group's first allocation
+  // six quantisers whatever the picture and is allocated with the group's first allocation
   DevBuf fr_jobs_y, fr_jobs_c, fr_res_y, fr_res_c, fr_quant, fr_modes;
   int fr_capacity = 0, fr_n = 0;
   DevBuf fr_rec;                                      // fused frame stage: one JmMbRes (4:2:2: jmhip_mb_residual422) record per macroblock (frame_common.h)
@@ -84,13 +86,14 @@ struct jmhip_ctx {
   bool fr_fused422 = false;                           // ... its 4:2:2 form: the records are jmhip_mb_residual422
   DevBuf fr_rec8;                                     // ... and one jmhip_mb_residual8 per macroblock when the picture has 8x8-transform macroblocks
   bool fr_fused8 = false;                             // the last fused stage was the 8x8-transform instantiation: fr_rec8 holds its side records
+  bool fr_fused444 = false;                           // ... the 4:4:4 stage (frame444.hip): jmhip_mb_residual444 records, three side records per macroblock
   DevBuf fr_blk_ref;                                  // [n][4] reference slot per 8x8 block (frame stage fed from the slice search)
   bool fr_slices_t8 = false;                          // ... and some of them may carry the 8x8-transform flag (Transform8x8Mode in the slice search)
   bool fr_from_slices = false;                        // modes + per-block references of the frame stage were left on the device by jmhip_slice_to_frame
   DevBuf fr_bi; int fr_bi_n = 0; unsigned fr_bi_mask = 0;   // second list of B macroblocks (jmhip_frame_bipred_set), device array
   jmhip_frame_bw fr_bw{};
   jmhip_frame_wp fr_wp{};                             // explicit weighted prediction of the frame stage (enable = 0: off)
-  jmhip_quant fr_quant_host[4];
+  jmhip_quant fr_quant_host[6];                       // (4:4:4: 4x4 quantisers of Y, Cb, Cr, then their 8x8 ones)
   DevBuf rec_y, rec_u, rec_v;                         // all three or none (jm_ensure_recon)
   DevBuf pred_y, pred_u, pred_v;                      // jmhip_frame_keep_prediction: the prediction picture of the last fused frame stage
   bool keep_pred = false, pred_valid = false;
@@ -138,6 +141,10 @@ int jm_download_planes(jmhip_ctx *c, const uint8_t *src, size_t n, void *out, in
 // kernels (one translation unit each)
 int jm_launch_interp_luma(jmhip_ctx *ctx, int ref, int prow0 = 0, int prow1 = 0);
 int jm_launch_interp_chroma(jmhip_ctx *ctx, int ref, int prow0 = 0, int prow1 = 0);
+int jm_launch_interp_luma_plane(jmhip_ctx *ctx, const uint8_t *src, uint8_t *out, int prow0 = 0, int prow1 = 0);   // interp_luma_kernel on any plane of the luma geometry
+// frame444.hip: the 4:4:4 frame stage and the expansion of its records
+int jm_residual_frame444(jmhip_ctx *ctx, const jmhip_mb_mode *modes, const jmhip_quant *quants, int nquants);
+int jm_residual_download444(jmhip_ctx *ctx, jmhip_tq_result *luma, jmhip_tq_result *chroma, int n);
 constexpr int JMHIP_TQ_SELECT = 0x100;   // frame stage: each luma kernel takes only the macroblocks of its transform size
 int jm_launch_tq(jmhip_ctx *ctx, int kind, int yuv_format, const void *jobs, const void *quants, void *results, int n);
 int jm_ensure_ref_table(jmhip_ctx *ctx);

@@ -158,6 +158,10 @@ MB_RESIDUAL422_DTYPE = np.dtype([("lev", "<i2", (32, 16)), ("run", "u1", (32, 16
                                  ("fadj_c", "<i2", (2, 16, 8)), ("recon_y", "u1", (16, 16)), ("recon_c", "u1", (2, 16, 8)), ("pad2", "u1", (8,))])      # jmhip_mb_residual422
 MB_RESIDUAL8_DTYPE = np.dtype([("lev", "<i2", (4, 64)), ("run", "u1", (4, 64)), ("cnt", "u1", (4, 4)), ("coeff_cost", "<i4", (4,)), ("nonzero", "<i4", (4,)),
                                ("transform8x8", "<i4"), ("interleaved", "<i4"), ("pad", "u1", (8,))])      # jmhip_mb_residual8
+MB_RESIDUAL444_DTYPE = np.dtype([("lev", "<i2", (3, 16, 16)), ("run", "u1", (3, 16, 16)), ("cnt", "u1", (3, 16)), ("coeff_cost", "<i4", (3, 16)),
+                                 ("nonzero", "<u2", (3,)), ("cleared8", "u1", (3,)), ("cleared_mb", "u1", (3,)), ("plane_cbp", "<i4", (3,)),
+                                 ("plane_cbp_blk", "<i4", (3,)), ("cbp", "<i4"), ("pad0", "<i4", (2,)), ("fadj", "<i2", (3, 16, 16)),
+                                 ("recon", "u1", (3, 16, 16))])      # jmhip_mb_residual444: index 0 Y, 1 Cb, 2 Cr
 TQ_RESULT_DTYPE = np.dtype([("levels", "<i4", (16, 17)), ("runs", "<i4", (16, 17)), ("levels8", "<i4", (4, 65)), ("runs8", "<i4", (4, 65)),
                             ("dc_levels", "<i4", (17,)), ("dc_runs", "<i4", (17,)), ("recon", "u1", (16, 16)), ("fadjust", "<i4", (16, 16)),
                             ("coeff_cost", "<i4", (16,)), ("nonzero", "<i4", (16,)), ("ret", "<i4"), ("cbp_blk", "<i8"), ("cbp_clear", "<i8")],
@@ -226,6 +230,9 @@ def load_library():
     lib.jmhip_residual_records_download.argtypes = [vp, vp, ip]
     lib.jmhip_residual_records8_download.argtypes = [vp, vp, ip]
     lib.jmhip_residual_records422_download.argtypes = [vp, vp, ip]
+    lib.jmhip_interp_chroma444.argtypes = [vp, ip]
+    lib.jmhip_residual_records444_download.argtypes = [vp, vp, ip]
+    lib.jmhip_residual_records8_444_download.argtypes = [vp, vp, ip]
     lib.jmhip_frame_keep_prediction.argtypes = [vp, ip]
     lib.jmhip_pred_download.argtypes = [vp, vp, vp, vp, ip]
     lib.jmhip_recon_copy_band.argtypes = [vp, vp, vp, vp, ip, ip]
@@ -266,7 +273,7 @@ def load_library():
     lib.jmhip_frame_bipred_set.argtypes = [vp, vp, ip, vp]
     for which, dt in ((0, ME_MB_DTYPE), (1, ME_RESULT_DTYPE), (2, QUANT_DTYPE), (3, TQ_JOB_DTYPE), (4, TQ_RESULT_DTYPE),
                       (5, DIST_JOB_DTYPE), (8, MB_MODE_DTYPE), (9, SURFACE_JOB_DTYPE), (10, BIPRED_JOB_DTYPE), (11, BIPRED_RESULT_DTYPE), (13, PREDCOST_JOB_DTYPE),
-                      (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE), (24, MB_RESIDUAL422_DTYPE),
+                      (14, DEBLOCK_MB_DTYPE), (15, DEBLOCK_BLK_DTYPE), (18, MB_INTER_DTYPE), (23, MB_RESIDUAL8_DTYPE), (24, MB_RESIDUAL422_DTYPE), (26, MB_RESIDUAL444_DTYPE),
                       (30, BIPRED_CHAIN_JOB_DTYPE), (32, BIPRED_CHAIN_RESULT_DTYPE), (33, BIPRED_SURFACE_JOB_DTYPE)):
         if lib.jmhip_sizeof(which) != dt.itemsize:
             raise JmhipError("binding layout mismatch for struct %d: C %d vs numpy %d" % (which, lib.jmhip_sizeof(which), dt.itemsize))
@@ -399,6 +406,11 @@ class Context:
 
     def interp_chroma(self, ref):
         self._chk(self.lib.jmhip_interp_chroma(self.h, ref), "jmhip_interp_chroma")
+
+    def interp_chroma444(self, ref):
+        """4:4:4 contexts: the 6-tap quarter-pel Cb / Cr planes JM predicts 4:4:4 chroma from (getSubImagesLuma per plane); download_chroma_planes
+        and download_chroma_rows deliver them as they deliver interp_chroma's."""
+        self._chk(self.lib.jmhip_interp_chroma444(self.h, ref), "jmhip_interp_chroma444")
 
     def download_luma_planes(self, ref, dtype=np.uint8):
         out = np.empty((4, 4, self.Hp, self.Wp), dtype=dtype)
@@ -605,9 +617,9 @@ class Context:
 
     # ---- frame stage: MC -> residual -> TQ -> recon
     def residual_frame(self, quants, modes=None):
-        """quants: 3 quantisers (luma 4x4, chroma, chroma DC) or 4 (+ the 8x8 luma quantiser, for modes with pad[0] = 1)."""
+        """quants: 3 quantisers (luma 4x4, chroma, chroma DC) or 4 (+ the 8x8 luma quantiser, for modes with pad[0] = 1). In a 4:4:4 context:
+        3 (the 4x4 quantisers of Y, Cb, Cr) or 6 (+ their 8x8 quantisers); the library checks the count."""
         quants = np.ascontiguousarray(quants, dtype=QUANT_DTYPE)
-        assert len(quants) in (3, 4)
         if modes is not None:
             modes = np.ascontiguousarray(modes, dtype=MB_MODE_DTYPE)
         self._chk(self.lib.jmhip_residual_frame_q(self.h, _ptr(modes), _ptr(quants), len(quants)), "jmhip_residual_frame")
@@ -647,6 +659,18 @@ class Context:
         """The dense per-macroblock records (jmhip_mb_residual422) of the last fused 4:2:2 residual_frame."""
         rec = np.zeros(n, MB_RESIDUAL422_DTYPE)
         self._chk(self.lib.jmhip_residual_records422_download(self.h, _ptr(rec), n), "jmhip_residual_records422_download")
+        return rec
+
+    def residual_records444(self, n):
+        """The dense per-macroblock records (jmhip_mb_residual444: Y, Cb, Cr through the luma path) of the last 4:4:4 residual_frame."""
+        rec = np.zeros(n, MB_RESIDUAL444_DTYPE)
+        self._chk(self.lib.jmhip_residual_records444_download(self.h, _ptr(rec), n), "jmhip_residual_records444_download")
+        return rec
+
+    def residual_records8_444(self, n):
+        """(n, 3) 8x8-transform side records (jmhip_mb_residual8) of the last 4:4:4 residual_frame, one per macroblock and plane."""
+        rec = np.zeros((n, 3), MB_RESIDUAL8_DTYPE)
+        self._chk(self.lib.jmhip_residual_records8_444_download(self.h, _ptr(rec), n), "jmhip_residual_records8_444_download")
         return rec
 
     def residual_records8(self, n):

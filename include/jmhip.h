@@ -9,7 +9,9 @@
  * launch per FRAME stage. A context owns device-resident pictures:
  *   reference slots  -- integer-pel recon + the 16 quarter-pel luma planes + the 8x8 (4:2:0) / 4x8 (4:2:2)
  *                       / 4x4 (4:4:4) eighth-pel chroma planes, exactly the arrays JM's StorablePicture
- *                       holds after UnifiedOneForthPix (src/image.c:1601), as 8-bit samples;
+ *                       holds after UnifiedOneForthPix (src/image.c:1601), as 8-bit samples; for 4:4:4 the chroma
+ *                       buffers hold either those bilinear planes or the 6-tap planes JM predicts 4:4:4 Cb / Cr
+ *                       from (jmhip_interp_chroma444);
  *   the current picture (source samples);
  *   per-macroblock job/result arrays of the stage calls below.
  * Calls enqueue on the context's HIP stream and return; jmhip_sync() (or any download) completes them.
@@ -722,8 +724,51 @@ typedef struct jmhip_mb_residual422 {
   uint8_t pad2[8];
 } jmhip_mb_residual422;
 int jmhip_residual_records422_download(jmhip_ctx *ctx, jmhip_mb_residual422 *records, int n);
+
+/* ---- 4:4:4 pictures (joint coding, not the independent mode): JM sends Cb and Cr through the LUMA path, src/macroblock.c:1009-1449.
+ * Reference planes: UnifiedOneForthPix (src/image.c:1647-1656) runs getSubImagesLuma under select_plane(PLANE_U / PLANE_V), so the quarter-pel
+ * Cb / Cr planes of a 4:4:4 reference are 6-tap planes with the luma geometry ([16][H+40][W+40]), read with UMVLine4X by ChromaPrediction
+ * (src/macroblock.c:1712). jmhip_interp_chroma444 builds them into the slot's chroma plane buffers (JMHIP_YUV444 contexts only; the bilinear
+ * planes of jmhip_interp_chroma take the same buffers, so a slot holds one kind at a time -- the later call wins). jmhip_ref_download_chroma(_rows)
+ * deliver either kind; the chroma term of the motion search keeps asking for jmhip_interp_chroma's.
+ * Frame stage: jmhip_residual_frame_q in a JMHIP_YUV444 context takes nquants = 3 -- quants[0] Y, [1] Cb, [2] Cr 4x4 quantisers -- or 6 -- [3..5]
+ * the 8x8 quantisers of Y, Cb, Cr, each with transform8x8_flag = 1; needed when a macroblock carries the 8x8-transform flag. Every used reference
+ * needs jmhip_interp_luma and jmhip_interp_chroma444 (JMHIP_ERR_ARG otherwise: there is no on-the-fly chroma here). Per plane and macroblock:
+ * prediction per 4x4 (8x8) block with the block-origin clamp and the component's column of jmhip_frame_wp_set, dct_4x4 x16 (:1093, :1105-1107) or
+ * dct_8x8 x4 (:1185, :1197-1199), then the plane's OWN _LUMA_COEFF_COST_ (:1236-1290) and _LUMA_MB_COEFF_COST_ (:1386-1444) thresholds. For Cb / Cr JM
+ * zeroes the coefficient lists of what a threshold clears (:1268-1270, :1283-1285, :1426-1429, :1440-1443), for Y it does not (the memset is commented
+ * out): the record follows JM in both. cbp = cbp_Y | cmp_cbp[0] | cmp_cbp[1] (:1446-1447; no chroma bits above bit 3), cbp_blk = the Y plane's bits 0..15.
+ * One launch whatever the transform sizes; JMHIP_FRAME_FUSED has no meaning here (there are no separate kernels for 4:4:4).
+ * JMHIP_ERR_UNSUPPORTED: a second list (jmhip_frame_bipred_set), modes handed over by jmhip_slice_to_frame*, adapt_rnd_weight outside 0..32767, and
+ * jmhip_deblock_recon afterwards (its strengths would have to read three planes' coded bits; jmhip_deblock_frame works as for every format). */
+int jmhip_interp_chroma444(jmhip_ctx *ctx, int ref);
+/* The dense per-macroblock record of the 4:4:4 frame stage (4896 bytes). Index 0 Y, 1 Cb, 2 Cr; per plane the luma fields of jmhip_mb_residual with
+ * the same meaning. In a plane of an 8x8-transform macroblock lev / run / cnt / coeff_cost / nonzero read 0 and its lists are in the plane's
+ * jmhip_mb_residual8 side record. Entries of lev / run past cnt, and fadj without adaptive rounding, read 0. */
+typedef struct jmhip_mb_residual444 {
+  int16_t lev[3][16][16];        /* (level) lists in scan order, blocks in JM order b8*4+b4; Cb / Cr: all 0 where a threshold cleared the block */
+  uint8_t run[3][16][16];
+  uint8_t cnt[3][16];            /* entries of each list; JM's 0 terminator follows them */
+  int32_t coeff_cost[3][16];     /* what dct_4x4 adds to *coeff_cost, per 4x4 block (before the thresholds) */
+  uint16_t nonzero[3];           /* bit blk = dct_4x4's return value (before the thresholds) */
+  uint8_t cleared8[3];           /* bit b8: the 8x8 block's summed coeff_cost was <= _LUMA_COEFF_COST_ (reconstructed as its prediction) */
+  uint8_t cleared_mb[3];         /* 1: the plane's sum over the surviving blocks was <= _LUMA_MB_COEFF_COST_ (the whole plane is its prediction) */
+  int32_t plane_cbp[3];          /* currMB->cbp bits 0..3 / cmp_cbp[0] / cmp_cbp[1] after the thresholds */
+  int32_t plane_cbp_blk[3];      /* currMB->cbp_blk bits 0..15 / cur_cbp_blk[1] / cur_cbp_blk[2] after the thresholds */
+  int32_t cbp;                   /* currMB->cbp as LumaResidualCoding leaves it: the OR of the three */
+  int32_t pad0[2];
+  int16_t fadj[3][16][16];       /* adaptive rounding only: img->fadjust4x4 / fadjust8x8 (Cb / Cr: ...Cr[uv]) */
+  uint8_t recon[3][16][16];      /* the transform path's reconstruction, as dct_4x4 / dct_8x8 write it (before the thresholds) */
+} jmhip_mb_residual444;
+int jmhip_residual_records444_download(jmhip_ctx *ctx, jmhip_mb_residual444 *records, int n);
+/* The 8x8-transform side records of a 4:4:4 stage: records[i * 3 + plane], all zero for macroblocks without the flag (and for every macroblock when
+ * the stage had none). Cb / Cr: the lists and counts of a block that a threshold cleared read 0; coeff_cost / nonzero stay what dct_8x8 returned. */
+int jmhip_residual_records8_444_download(jmhip_ctx *ctx, jmhip_mb_residual8 *records, int n);
+/* After a 4:4:4 stage jmhip_residual_download expands chroma[2 * i + uv] in the luma shape (sixteen lists, levels8 / runs8 for 8x8-transform
+ * macroblocks, 16x16 recon / fadjust) with ret = the plane's cbp, cbp_blk = the plane's cbp_blk, cbp_clear = 0; jmhip_residual_records_download,
+ * jmhip_residual_records422_download and jmhip_residual_records8_download answer JMHIP_ERR_UNSUPPORTED; jmhip_pred_download delivers three full-size planes. */
 /* Keep the prediction picture -- img->mpr of every macroblock of jmhip_residual_frame, luma and chroma (src/macroblock.c:836, :1593) -- beside
- * the recon picture (fused 4:2:0 / 4:2:2 stage only), and copy it to the host (pel_bytes 1 or 2): a binding that answers JM's LumaPrediction /
+ * the recon picture (fused 4:2:0 / 4:2:2 stage and the 4:4:4 stage), and copy it to the host (pel_bytes 1 or 2): a binding that answers JM's LumaPrediction /
  * ChromaPrediction4x4 from the device reads it, and checks its dct inputs against it. */
 int jmhip_frame_keep_prediction(jmhip_ctx *ctx, int on);
 int jmhip_pred_download(jmhip_ctx *ctx, void *Y, void *U, void *V, int pel_bytes);
@@ -788,7 +833,7 @@ int jmhip_ref_unpack_bands(jmhip_ctx *ctx, int ref, const void *chunks_device, i
  * 2 jmhip_quant, 3 jmhip_tq_job, 4 jmhip_tq_result, 5 jmhip_dist_job, 6 jmhip_me_params, 7 jmhip_config,
  * 8 jmhip_mb_mode, 9 jmhip_surface_job, 10 jmhip_bipred_job, 11 jmhip_bipred_result, 12 jmhip_bipred_params, 13 jmhip_predcost_job,
  * 14 jmhip_deblock_mb, 15 jmhip_deblock_blk, 16 jmhip_deblock_params, 17 jmhip_slice_params, 18 jmhip_mb_inter, 19 jmhip_frame_wp,
- * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8, 24 jmhip_mb_residual422 (25..29: none, -1),
+ * 20 jmhip_mb_bipred, 21 jmhip_frame_bw, 22 jmhip_mb_residual, 23 jmhip_mb_residual8, 24 jmhip_mb_residual422, 26 jmhip_mb_residual444 (25, 27..29: none, -1),
  * 30 jmhip_bipred_chain_job, 31 jmhip_bipred_chain_params, 32 jmhip_bipred_chain_result, 33 jmhip_bipred_surface_job. */
 int jmhip_sizeof(int which);
 
