@@ -10,7 +10,7 @@
 //   ChromaResidualCoding: cr_cbp chained over U,V, cbp += cr_cbp<<4   macroblock.c:1944-2044
 // The transform/quant itself is tq.hip's dct_4x4 / dct_chroma kernels run over device-resident job arrays.
 // Which mode a macroblock takes is the host's decision (JM's mode decision is out of scope); without one the
-// device picks the partitioning with the smallest summed motion cost.
+// device picks the partitioning itself (pick_mode, frame_common.h).
 #include "jmhip_internal.h"
 #include <utility>
 #include <vector>
@@ -35,27 +35,7 @@ __global__ __launch_bounds__(64) void mc_kernel(FrameDev F, const jmhip_me_mb *_
   const int mbx = mb.mb_x, mby = mb.mb_y;
 
   if (tid == 0) {
-    jmhip_mb_mode m;
-    if (modes_in) m = modes_in[i];
-    else {
-      // smallest summed motion cost; ties go to the lower mode number
-      const int *c = r.cost;
-      int c8 = 0;
-      for (int b = 0; b < 4; b++) {
-        const int s4 = c[5 + b], s5 = c[9 + 2 * b] + c[10 + 2 * b], s6 = c[17 + 2 * b] + c[18 + 2 * b];
-        const int s7 = c[25 + 4 * b] + c[26 + 4 * b] + c[27 + 4 * b] + c[28 + 4 * b];
-        int best = s4, bm = 4;
-        if (s5 < best) { best = s5; bm = 5; }
-        if (s6 < best) { best = s6; bm = 6; }
-        if (s7 < best) { best = s7; bm = 7; }
-        m.b8mode[b] = (int8_t)bm; c8 += best;
-      }
-      int best = c[0]; m.mode = 1;
-      if (c[1] + c[2] < best) { best = c[1] + c[2]; m.mode = 2; }
-      if (c[3] + c[4] < best) { best = c[3] + c[4]; m.mode = 3; }
-      if (c8 < best) { best = c8; m.mode = 8; }
-      m.pad[0] = m.pad[1] = m.pad[2] = 0;
-    }
+    const jmhip_mb_mode m = modes_in ? modes_in[i] : pick_mode(r.cost);
     s_mode = m;
     modes_out[i] = m;
   }
@@ -80,8 +60,8 @@ __global__ __launch_bounds__(64) void mc_kernel(FrameDev F, const jmhip_me_mb *_
     if (F.bi) { const jmhip_mb_bipred &bm = F.bi[i]; pdir = bm.pdir[b8]; slot1 = bm.ref1[b8]; xq1 = bqx + bm.mv1[tid][0]; yq1 = bqy + bm.mv1[tid][1]; }
 #pragma unroll
     for (int rr = 0; rr < 4; rr++) {
-      const uint32_t v0 = pdir != 1 ? luma_row4(F, slot, xq, yq, ox4, oy4, rr) : 0u;
-      const uint32_t v1 = pdir != 0 ? luma_row4(F, slot1, xq1, yq1, ox4, oy4, rr) : 0u;
+      const uint32_t v0 = pdir != 1 ? luma_row4(F, F.ref_sub, slot, xq, yq, ox4, oy4, rr) : 0u;
+      const uint32_t v1 = pdir != 0 ? luma_row4(F, F.ref_sub, slot1, xq1, yq1, ox4, oy4, rr) : 0u;
       uint32_t pv = v0;
       if (F.wp_on || pdir) {
         uint32_t w = 0;

@@ -10,99 +10,22 @@
 // :1440-1443); for Y the memset is commented out (:1244-1248, :1395-1402) and the lists stay as dct_4x4 / dct_8x8 left them.
 //
 // Kernel shape: four macroblocks per workgroup of three waves, wave <-> colour plane; inside a wave the lane map of frame_fused_kernel's luma
-// phase (tq.hip): lane <-> 4x4 block in JM's block order, DPP quad <-> 8x8 block. The arithmetic is that phase's, line for line; the small
-// transform helpers are restated here because tq.hip keeps its own in its translation unit. The planes meet once, through LDS, for the
-// macroblock's cbp. Records are assembled in LDS (zeroed first, so that every byte of a record is defined) and leave as 16-byte pieces.
+// phase (tq.hip): lane <-> 4x4 block in JM's block order, DPP quad <-> 8x8 block. The block itself is that phase's, the same code: luma_block
+// and luma_thresholds of frame_block.h, handed this wave's plane, its quantisers quants[pl] / [3 + pl], plane pl of the record, one reference per
+// macroblock and no second list. This kernel's own are what it records of the thresholds (cleared8, cleared_mb, plane_cbp*), the zeroing of
+// cleared Cb / Cr lists and the picture stores. The planes meet once, through LDS, for the macroblock's cbp. Records are assembled in LDS
+// (zeroed first, so that every byte of a record is defined) and leave as 16-byte pieces.
 #include "jmhip_internal.h"
 #include <cstring>
 #include <vector>
 
-#include "frame_common.h"
+#include "frame_block.h"
 
 static_assert(sizeof(jmhip_mb_residual444) % 16 == 0 && sizeof(jmhip_mb_residual8) % 16 == 0, "records are copied out of LDS as 16-byte pieces");
 static_assert(offsetof(jmhip_mb_residual444, run) % 16 == 0 && offsetof(jmhip_mb_residual8, run) % 16 == 0 && offsetof(jmhip_mb_residual8, cnt) % 4 == 0,
               "the lists of a cleared Cb / Cr block are zeroed with 16-byte stores");
 
 namespace {
-
-constexpr int Q_BITS = 15, Q_BITS_8 = 16, DQ_BITS = 6, MAXV = 999999;
-constexpr int LUMA_COEFF_COST = 4, LUMA_MB_COEFF_COST = 5;           // _LUMA_COEFF_COST_, _LUMA_MB_COEFF_COST_, inc/defines.h
-
-__constant__ uint8_t c_scan8[2][64][2] = {
-  {{0,0},{1,0},{0,1},{0,2},{1,1},{2,0},{3,0},{2,1},{1,2},{0,3},{0,4},{1,3},{2,2},{3,1},{4,0},{5,0},
-   {4,1},{3,2},{2,3},{1,4},{0,5},{0,6},{1,5},{2,4},{3,3},{4,2},{5,1},{6,0},{7,0},{6,1},{5,2},{4,3},
-   {3,4},{2,5},{1,6},{0,7},{1,7},{2,6},{3,5},{4,4},{5,3},{6,2},{7,1},{7,2},{6,3},{5,4},{4,5},{3,6},
-   {2,7},{3,7},{4,6},{5,5},{6,4},{7,3},{7,4},{6,5},{5,6},{4,7},{5,7},{6,6},{7,5},{7,6},{6,7},{7,7}},      // transform8x8.c:171
-  {{0,0},{0,1},{0,2},{1,0},{1,1},{0,3},{0,4},{1,2},{2,0},{1,3},{0,5},{0,6},{0,7},{1,4},{2,1},{3,0},
-   {2,2},{1,5},{1,6},{1,7},{2,3},{3,1},{4,0},{3,2},{2,4},{2,5},{2,6},{2,7},{3,3},{4,1},{5,0},{4,2},
-   {3,4},{3,5},{3,6},{3,7},{4,3},{5,1},{6,0},{5,2},{4,4},{4,5},{4,6},{4,7},{5,3},{6,1},{6,2},{5,4},
-   {5,5},{5,6},{5,7},{6,3},{7,0},{7,1},{6,4},{6,5},{6,6},{6,7},{7,2},{7,3},{7,4},{7,5},{7,6},{7,7}}};     // transform8x8.c:184
-__constant__ uint8_t c_cost4[2][16] = {{3,2,2,1,1,1,0,0,0,0,0,0,0,0,0,0}, {9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9}};   // block.h:45
-__constant__ uint8_t c_cost8[2][64] = {
-  {3,3,3,3,2,2,2,2,2,2,2,2,1,1,1,1,1,1,1,1,1,1,1,1,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0},
-  {9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9,9}};
-
-__device__ __forceinline__ int iabs(int x) { return x < 0 ? -x : x; }
-__device__ __forceinline__ int sgnab(int a, int b) { return b < 0 ? -iabs(a) : iabs(a); }      // isignab
-__device__ __forceinline__ int rsr(int x, int a) { return (x + (1 << (a - 1))) >> a; }          // rshift_rnd_sf
-// iClip1 -- the empty asm keeps hipcc from forming v_ashr_pk_u8_i32 (see interp_luma.hip)
-__device__ __forceinline__ int clip1(int hi, int v) { asm volatile("" : "+v"(v)); return min(max(v, 0), hi); }
-
-// forward4x4 / inverse4x4 on a register block b[row][col]   (transform.c:31, :81)
-__device__ __forceinline__ void fwd4(int b[4][4])
-{
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int t0 = b[i][0] + b[i][3], t1 = b[i][1] + b[i][2], t2 = b[i][1] - b[i][2], t3 = b[i][0] - b[i][3];
-    b[i][0] = t0 + t1; b[i][1] = (t3 << 1) + t2; b[i][2] = t0 - t1; b[i][3] = t3 - (t2 << 1);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int t0 = b[0][i] + b[3][i], t1 = b[1][i] + b[2][i], t2 = b[1][i] - b[2][i], t3 = b[0][i] - b[3][i];
-    b[0][i] = t0 + t1; b[1][i] = t2 + (t3 << 1); b[2][i] = t0 - t1; b[3][i] = t3 - (t2 << 1);
-  }
-}
-__device__ __forceinline__ void inv4(int b[4][4])
-{
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int p0 = b[i][0] + b[i][2], p1 = b[i][0] - b[i][2], p2 = (b[i][1] >> 1) - b[i][3], p3 = b[i][1] + (b[i][3] >> 1);
-    b[i][0] = p0 + p3; b[i][1] = p1 + p2; b[i][2] = p1 - p2; b[i][3] = p0 - p3;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int p0 = b[0][i] + b[2][i], p1 = b[0][i] - b[2][i], p2 = (b[1][i] >> 1) - b[3][i], p3 = b[1][i] + (b[3][i] >> 1);
-    b[0][i] = p0 + p3; b[1][i] = p1 + p2; b[2][i] = p1 - p2; b[3][i] = p0 - p3;
-  }
-}
-__device__ __forceinline__ void fwd8_1d(const int p[8], int o[8])      // transform.c:248-275
-{
-  int a0 = p[0] + p[7], a1 = p[1] + p[6], a2 = p[2] + p[5], a3 = p[3] + p[4];
-  const int b0 = a0 + a3, b1 = a1 + a2, b2 = a0 - a3, b3 = a1 - a2;
-  a0 = p[0] - p[7]; a1 = p[1] - p[6]; a2 = p[2] - p[5]; a3 = p[3] - p[4];
-  const int b4 = a1 + a2 + ((a0 >> 1) + a0), b5 = a0 - a3 - ((a2 >> 1) + a2);
-  const int b6 = a0 + a3 - ((a1 >> 1) + a1), b7 = a1 - a2 + ((a3 >> 1) + a3);
-  o[0] = b0 + b1; o[1] = b4 + (b7 >> 2); o[2] = b2 + (b3 >> 1); o[3] = b5 + (b6 >> 2);
-  o[4] = b0 - b1; o[5] = b6 - (b5 >> 2); o[6] = (b2 >> 1) - b3; o[7] = (b4 >> 2) - b7;
-}
-__device__ __forceinline__ void inv8_1d(const int p[8], int o[8])      // transform.c:346-373
-{
-  int a0 = p[0] + p[4], a1 = p[0] - p[4], a2 = p[6] - (p[2] >> 1), a3 = p[2] + (p[6] >> 1);
-  const int b0 = a0 + a3, b2 = a1 - a2, b4 = a1 + a2, b6 = a0 - a3;
-  a0 = -p[3] + p[5] - p[7] - (p[7] >> 1);
-  a1 =  p[1] + p[7] - p[3] - (p[3] >> 1);
-  a2 = -p[1] + p[7] + p[5] + (p[5] >> 1);
-  a3 =  p[3] + p[5] + p[1] + (p[1] >> 1);
-  const int b1 = a0 + (a3 >> 2), b3 = a1 + (a2 >> 2), b5 = a2 - (a1 >> 2), b7 = a3 - (a0 >> 2);
-  o[0] = b0 + b7; o[1] = b2 - b5; o[2] = b4 + b3; o[3] = b6 + b1;
-  o[4] = b6 - b1; o[5] = b4 - b3; o[6] = b2 + b5; o[7] = b0 - b7;
-}
-
-__device__ __forceinline__ void wave_lds_sync()       // LDS traffic between lanes of one wave: ordered, nothing more to wait for
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ int quad_first(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x00, 0xf, 0xf, false); }   // the quad's first lane's value
 
 // T8: the instantiation for pictures with 8x8-transform macroblocks (mode pad[0]); 4x4-only pictures never select it. An 8x8-transform
 // macroblock takes dct_8x8 in ALL THREE planes (macroblock.c:1185, :1197-1199), with quants[3 + plane]; out8 is [n][3], plane-minor.
@@ -145,26 +68,7 @@ __global__ __launch_bounds__(192) void frame_fused444_kernel(FrameDev F, const j
     for (int k = threadIdx.x; k < NMB * 3 * (int)(sizeof(jmhip_mb_residual8) / 16); k += 192) reinterpret_cast<uint4 *>(s_rec8)[k] = make_uint4(0, 0, 0, 0);
   __syncthreads();
   if (wv == 0 && tid < NMB) {
-    jmhip_mb_mode m;
-    if (modes_in) m = m_in;
-    else {                                             // smallest summed motion cost; ties go to the lower mode number (as mc_kernel)
-      const int *c = s_cost[tid];
-      int c8 = 0;
-      for (int b = 0; b < 4; b++) {
-        const int s4 = c[5 + b], s5 = c[9 + 2 * b] + c[10 + 2 * b], s6 = c[17 + 2 * b] + c[18 + 2 * b];
-        const int s7 = c[25 + 4 * b] + c[26 + 4 * b] + c[27 + 4 * b] + c[28 + 4 * b];
-        int best = s4, bm = 4;
-        if (s5 < best) { best = s5; bm = 5; }
-        if (s6 < best) { best = s6; bm = 6; }
-        if (s7 < best) { best = s7; bm = 7; }
-        m.b8mode[b] = (int8_t)bm; c8 += best;
-      }
-      int best = c[0]; m.mode = 1;
-      if (c[1] + c[2] < best) { best = c[1] + c[2]; m.mode = 2; }
-      if (c[3] + c[4] < best) { best = c[3] + c[4]; m.mode = 3; }
-      if (c8 < best) { best = c8; m.mode = 8; }
-      m.pad[0] = m.pad[1] = m.pad[2] = 0;
-    }
+    const jmhip_mb_mode m = modes_in ? m_in : pick_mode(s_cost[tid]);
     s_mode[tid] = m;
     if (tid < nlive) modes_out[i0 + tid] = m;
   }
@@ -176,232 +80,24 @@ __global__ __launch_bounds__(192) void frame_fused444_kernel(FrameDev F, const j
   }
   __syncthreads();
 
-  // ---- this wave's plane
-  const int pl = wv;
-  const uint8_t *__restrict__ cur = pl == 0 ? F.cur_y : (pl == 1 ? F.cur_u : F.cur_v);
-  const uint8_t *const *planes = pl == 0 ? F.ref_sub : (pl == 1 ? F.ref_cb : F.ref_cr);        // quarter-pel stacks, all of the luma geometry
-  uint8_t *__restrict__ rec_p = pl == 0 ? F.rec_y : (pl == 1 ? F.rec_u : F.rec_v);
-  uint8_t *__restrict__ pred_p = pl == 0 ? F.pred_y : (pl == 1 ? F.pred_u : F.pred_v);
+  // ---- this wave's plane through luma_block (frame_block.h): prediction by ChromaPrediction under select_plane for Cb / Cr (:1049-1055, :1144-1150),
+  // the plane's quantisers, plane pl of the record; one reference per macroblock and no second list (B macroblocks are refused on the host)
   {
-    // ---- one block: prediction (LumaPrediction / ChromaPrediction per 4x4 block, macroblock.c:836, :1712), residual, dct_4x4 (block.c:843)
-    const int h = tid >> 4, l = tid & 15;
-    const int mbx = s_pos[h][0], mby = s_pos[h][1];
-    const bool live = h < nlive;
-    Rec &R = s_rec[h];
-    const int blk = l, b8 = blk >> 2, b4 = blk & 3;
+    const int pl = wv;
+    const PlaneView P = {pl == 0 ? F.ref_sub : (pl == 1 ? F.ref_cb : F.ref_cr), pl == 0 ? F.cur_y : (pl == 1 ? F.cur_u : F.cur_v),
+                         pl == 0 ? F.rec_y : (pl == 1 ? F.rec_u : F.rec_v), pl == 0 ? F.pred_y : (pl == 1 ? F.pred_u : F.pred_v), pl};
+    const int h = tid >> 4, blk = tid & 15, b8 = blk >> 2, b4 = blk & 3;
     const int x4 = 2 * (b8 & 1) + (b4 & 1), y4 = 2 * (b8 >> 1) + (b4 >> 1), bx = 4 * x4, by = 4 * y4;
-    const jmhip_quant &q = quants[pl];
-    const int qp_per = q.qp / 6, q_bits = Q_BITS + qp_per;
-    // an 8x8-transform macroblock predicts per 8x8 block (:1143-1150): the clamp applies to the 8x8 origin, this 4x4 block sits at (ox4, oy4) in it
+    const int mbx = s_pos[h][0], mby = s_pos[h][1];
+    Rec &R = s_rec[h];
+    jmhip_mb_residual8 &R8 = s_rec8[T8 ? h : 0][pl];
     const bool t8 = T8 && s_mode[h].pad[0];
-    const int ox4 = t8 ? 4 * (b4 & 1) : 0, oy4 = t8 ? 4 * (b4 >> 1) : 0;
-    int m[4][4], pr[4][4];
-    {
-      const short *mv = s_mv[h][y4 * 4 + x4];
-      const int bqx = ((mbx * 16 + bx - ox4) << 2) + 4 * JMHIP_PAD, bqy = ((mby * 16 + by - oy4) << 2) + 4 * JMHIP_PAD;
-      const int xq = bqx + mv[0], yq = bqy + mv[1], slot = s_ref[h];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t v0 = luma_row4(F, planes, slot, xq, yq, ox4, oy4, j);
-        const uint32_t sv = *reinterpret_cast<const uint32_t *>(cur + (size_t)(mby * 16 + by + j) * F.W + mbx * 16 + bx);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          int p = (int)((v0 >> (8 * k)) & 255u);
-          if (F.wp_on) p = mix_pred(F, 0, slot, 0, pl, p, 0);            // the component's weights; Cb / Cr: the chroma round and denominator (:1784-1791)
-          pr[j][k] = p; m[j][k] = (int)((sv >> (8 * k)) & 255u) - p;     // img->m7[pl], macroblock.c:1059-1085
-        }
-      }
-    }
-    int nonzero = 0, cost = 0;                         // dct_4x4 per lane, or (8x8 transform) the quad's dct_8x8: cost on its first lane, the return value on all four
-    uint32_t rec[4], prd[4];
-    bool done = false;
-    if constexpr (T8) if (t8) {
-      // ---- dct_8x8 (transform8x8.c:1452-1653) on the quad of this 8x8 block, through the block's LDS tile
-      const jmhip_quant &q8 = quants[3 + pl];
-      const int qp8 = q8.qp / 6, qb8 = Q_BITS_8 + qp8;
-      const bool interleave = q8.transform8x8_flag && q8.cavlc;                       // transform8x8.c:1502
-      int *T = s_t8[(pl * NMB + h) * 4 + b8];
-      jmhip_mb_residual8 &R8 = s_rec8[h][pl];
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) T[(oy4 + j) * 8 + ox4 + k] = m[j][k];
-      wave_lds_sync();
-      // forward8x8 (transform.c:229): rows, then columns; lane b4 of the quad takes rows / columns 2*b4 and 2*b4+1
-#pragma unroll
-      for (int rr = 0; rr < 2; rr++) {
-        int p[8], o[8];
-        const int r = 2 * b4 + rr;
-#pragma unroll
-        for (int i = 0; i < 8; i++) p[i] = T[r * 8 + i];
-        fwd8_1d(p, o);
-#pragma unroll
-        for (int i = 0; i < 8; i++) T[r * 8 + i] = o[i];
-      }
-      wave_lds_sync();
-#pragma unroll
-      for (int cc = 0; cc < 2; cc++) {
-        int p[8], o[8];
-        const int c = 2 * b4 + cc;
-#pragma unroll
-        for (int j = 0; j < 8; j++) p[j] = T[j * 8 + c];
-        fwd8_1d(p, o);
-#pragma unroll
-        for (int j = 0; j < 8; j++) T[j * 8 + c] = o[j];
-      }
-      wave_lds_sync();
-      // quantisation is element-wise (rows 2*b4, 2*b4+1): the signed level replaces the coefficient; fadjust8x8 beside it
-#pragma unroll
-      for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const int j = 2 * b4 + rr, idx = j * 8 + i, c = T[idx];
-          const int scaled = iabs(c) * q8.levelscale[idx];
-          const int level = (scaled + q8.leveloffset[idx]) >> qb8;
-          if (q8.adaptive_rounding) R.fadj[pl][8 * (b8 >> 1) + j][8 * (b8 & 1) + i] = (int16_t)(level ? rsr(q8.adapt_rnd_weight * (scaled - (level << qb8)), qb8 + 1) : 0);
-          T[idx] = level ? sgnab(level, c) : 0;
-        }
-      wave_lds_sync();
-      // the run / level lists are sequential: the quad's first lane walks the 64 scan positions
-      int nz8 = 0;
-      if (b4 == 0) {
-        int run = -1, sp = 0, c8 = 0;
-        int sp4[4] = {0, 0, 0, 0}, run4[4] = {-1, -1, -1, -1};
-        for (int k0 = 0; k0 < 64; k0 += 4) {
-#pragma unroll
-          for (int mc = 0; mc < 4; mc++) {                                             // mc = k & 3: the interleaved list of position k
-            const int k = k0 + mc, i = c_scan8[q8.field_scan][k][0], j = c_scan8[q8.field_scan][k][1];
-            const int lev = T[j * 8 + i];
-            run++; run4[mc]++;
-            if (lev) {
-              nz8 = 1;
-              if (interleave) {
-                c8 += iabs(lev) > 1 ? MAXV : c_cost8[q8.disthres][run4[mc]];
-                R8.lev[b8][16 * mc + sp4[mc]] = (int16_t)lev; R8.run[b8][16 * mc + sp4[mc]] = (uint8_t)run4[mc];
-                sp4[mc]++; run4[mc] = -1;
-              } else {
-                c8 += iabs(lev) > 1 ? MAXV : c_cost8[q8.disthres][run];
-                R8.lev[b8][sp] = (int16_t)lev; R8.run[b8][sp] = (uint8_t)run;
-                sp++; run = -1;
-              }
-            }
-          }
-        }
-        if (interleave) {
-#pragma unroll
-          for (int mc = 0; mc < 4; mc++) R8.cnt[b8][mc] = (uint8_t)sp4[mc];
-        } else R8.cnt[b8][0] = (uint8_t)sp;
-        R8.coeff_cost[b8] = c8; R8.nonzero[b8] = nz8;
-        if (b8 == 0) { R8.transform8x8 = 1; R8.interleaved = interleave ? 1 : 0; }
-        cost = c8;
-      }
-      nz8 = quad_first(nz8);
-      nonzero = nz8;
-      wave_lds_sync();
-      // dequantisation (transform8x8.c:1543) and inverse8x8 (transform.c:325) when the block has a level
-#pragma unroll
-      for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const int idx = (2 * b4 + rr) * 8 + i, lev = T[idx];
-          T[idx] = lev ? rsr((lev * q8.invlevelscale[idx]) << qp8, 6) : 0;
-        }
-      if (nz8) {
-        wave_lds_sync();
-#pragma unroll
-        for (int rr = 0; rr < 2; rr++) {
-          int p[8], o[8];
-          const int r = 2 * b4 + rr;
-#pragma unroll
-          for (int i = 0; i < 8; i++) p[i] = T[r * 8 + i];
-          inv8_1d(p, o);
-#pragma unroll
-          for (int i = 0; i < 8; i++) T[r * 8 + i] = o[i];
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int cc = 0; cc < 2; cc++) {
-          int p[8], o[8];
-          const int c = 2 * b4 + cc;
-#pragma unroll
-          for (int j = 0; j < 8; j++) p[j] = T[j * 8 + c];
-          inv8_1d(p, o);
-#pragma unroll
-          for (int j = 0; j < 8; j++) T[j * 8 + c] = o[j];
-        }
-      }
-      wave_lds_sync();
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        uint32_t w = 0, pw = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int v = nz8 ? clip1(q8.max_val, rsr(T[(oy4 + j) * 8 + ox4 + k], DQ_BITS) + pr[j][k]) : pr[j][k];
-          w |= (uint32_t)v << (8 * k); pw |= (uint32_t)pr[j][k] << (8 * k);
-        }
-        rec[j] = w; prd[j] = pw;
-        *reinterpret_cast<uint32_t *>(&R.recon[pl][by + j][bx]) = w;
-      }
-      done = true;                                     // (the 4x4 fields of the record read zero for this macroblock: the record was zeroed)
-    }
-    if (!done) {
-      fwd4(m);
-      int scan_pos = 0, run = -1;
-      int fa[4][4];
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        constexpr int I0[16] = {0,1,0,0,1,2,3,2,1,0,1,2,3,3,2,3}, J0[16] = {0,0,1,2,1,0,0,1,2,3,3,2,1,2,3,3};
-        constexpr int I1[16] = {0,0,1,0,0,1,1,1,2,2,2,2,3,3,3,3}, J1[16] = {0,1,0,2,3,1,2,3,0,1,2,3,0,1,2,3};
-        const int i0 = I0[k], j0 = J0[k], i1 = I1[k], j1 = J1[k];
-        const int c = q.field_scan ? m[j1][i1] : m[j0][i0];
-        const int idx = q.field_scan ? (j1 * 4 + i1) : (j0 * 4 + i0);
-        run++;
-        const int scaled = iabs(c) * q.levelscale[idx];
-        int level = (scaled + q.leveloffset[idx]) >> q_bits;
-        int deq = 0, fadj = 0;
-        if (level != 0) {
-          if (q.adaptive_rounding) fadj = rsr(q.adapt_rnd_weight * (scaled - (level << q_bits)), q_bits + 1);   // block.c:898
-          nonzero = 1;
-          cost += (level > 1) ? MAXV : c_cost4[q.disthres][run];
-          level = sgnab(level, c);
-          R.lev[pl][blk][scan_pos] = (int16_t)level; R.run[pl][blk][scan_pos] = (uint8_t)run; scan_pos++;
-          deq = rsr((level * q.invlevelscale[idx]) << qp_per, 4);                                             // block.c:907
-          run = -1;
-        }
-        if (q.field_scan) { m[j1][i1] = deq; fa[j1][i1] = fadj; } else { m[j0][i0] = deq; fa[j0][i0] = fadj; }
-      }
-      R.cnt[pl][blk] = (uint8_t)scan_pos;
-      R.coeff_cost[pl][blk] = cost;
-      if (q.adaptive_rounding) {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-          for (int k = 0; k < 4; k++) R.fadj[pl][by + j][bx + k] = (int16_t)fa[j][k];
-      }
-      if (scan_pos) inv4(m);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        uint32_t w = 0, pw = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int v = scan_pos ? clip1(q.max_val, rsr(m[j][k], DQ_BITS) + pr[j][k]) : pr[j][k];                // block.c:934 / :942
-          w |= (uint32_t)v << (8 * k); pw |= (uint32_t)pr[j][k] << (8 * k);
-        }
-        rec[j] = w; prd[j] = pw;
-        *reinterpret_cast<uint32_t *>(&R.recon[pl][by + j][bx]) = w;
-      }
-    }
-    // ---- the plane's own _LUMA_COEFF_COST_ per 8x8 block (a quad) and _LUMA_MB_COEFF_COST_ per macroblock: macroblock.c:1236-1290, :1386-1444
-    int cost8 = cost;
-    cost8 += __builtin_amdgcn_update_dpp(cost8, cost8, 0xB1, 0xf, 0xf, false);
-    cost8 += __builtin_amdgcn_update_dpp(cost8, cost8, 0x4E, 0xf, 0xf, false);
-    const bool keep8 = cost8 > LUMA_COEFF_COST;
-    int sum = keep8 ? cost8 : 0;
-    sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);
-    const bool keep_mb = sum > LUMA_MB_COEFF_COST, keep = keep8 && keep_mb;
-    int bits = (nonzero && keep) ? ((1 << (x4 + 4 * y4)) | (0x10000 << b8)) : 0;      // cbp_blk bit (block_x>>2) + block_y, :1045; the plane's cbp bit b8 above it
-    bits |= __shfl_xor(bits, 1); bits |= __shfl_xor(bits, 2); bits |= __shfl_xor(bits, 4); bits |= __shfl_xor(bits, 8);
-    const unsigned long long nz = __ballot(nonzero != 0 && !t8), gone = __ballot(!keep8);
+    const BlockRecord V = {R.lev[pl], R.run[pl], R.cnt[pl], R.coeff_cost[pl], R.fadj[pl], R.recon[pl], &R8};
+    const BlockOut o = luma_block<T8>(F, P, quants[pl], quants[T8 ? 3 + pl : pl], V, s_t8[T8 ? (pl * NMB + h) * 4 + b8 : 0], blk, mbx, mby, t8, s_ref[h],
+                                      s_mv[h][y4 * 4 + x4], NO_SECOND_LIST);    // (the 4x4 fields of an 8x8-transform macroblock read zero: the record was zeroed)
+    const LumaKeep th = luma_thresholds(blk, o.cost, o.nonzero);
+    const bool keep = th.keep8 && th.keep_mb;
+    const unsigned long long nz = __ballot(o.nonzero != 0 && !t8), gone = __ballot(!th.keep8);
     if (pl != 0 && !keep) {
       // Cb / Cr: memset(img->cofAC[block8x8 + 4 (+ 4)], 0, ...) -- levels and runs of every list of the cleared block (:1268-1270, :1283-1285, :1426-1429, :1440-1443)
       if (!t8) {
@@ -410,7 +106,6 @@ __global__ __launch_bounds__(192) void frame_fused444_kernel(FrameDev F, const j
         R.cnt[pl][blk] = 0;
       } else if constexpr (T8) {
         if (b4 == 0) {
-          jmhip_mb_residual8 &R8 = s_rec8[h][pl];
 #pragma unroll
           for (int k = 0; k < 8; k++) reinterpret_cast<uint4 *>(R8.lev[b8])[k] = make_uint4(0, 0, 0, 0);
 #pragma unroll
@@ -419,20 +114,20 @@ __global__ __launch_bounds__(192) void frame_fused444_kernel(FrameDev F, const j
         }
       }
     }
-    if (l == 0) {
+    if (blk == 0) {
       const unsigned g = (unsigned)(gone >> (16 * h)) & 0x1111u;                     // the first lane of each quad
       R.nonzero[pl] = (uint16_t)(nz >> (16 * h));
       R.cleared8[pl] = (uint8_t)((g & 1u) | ((g >> 3) & 2u) | ((g >> 6) & 4u) | ((g >> 9) & 8u));
-      R.cleared_mb[pl] = keep_mb ? 0 : 1;
-      R.plane_cbp[pl] = bits >> 16; R.plane_cbp_blk[pl] = bits & 0xffff;
+      R.cleared_mb[pl] = th.keep_mb ? 0 : 1;
+      R.plane_cbp[pl] = th.bits >> 16; R.plane_cbp_blk[pl] = th.bits & 0xffff;
     }
-    if (live) {
+    if (h < nlive) {
 #pragma unroll
       for (int j = 0; j < 4; j++)
-        *reinterpret_cast<uint32_t *>(rec_p + (size_t)(mby * 16 + by + j) * F.W + mbx * 16 + bx) = keep ? rec[j] : prd[j];
-      if (pred_p) {                                    // img->mpr[pl], kept for a host that answers JM's predictions from it (jmhip_frame_keep_prediction)
+        *reinterpret_cast<uint32_t *>(P.rec + (size_t)(mby * 16 + by + j) * F.W + mbx * 16 + bx) = keep ? o.rec[j] : o.prd[j];
+      if (P.pred) {                                    // img->mpr[pl], kept for a host that answers JM's predictions from it (jmhip_frame_keep_prediction)
 #pragma unroll
-        for (int j = 0; j < 4; j++) *reinterpret_cast<uint32_t *>(pred_p + (size_t)(mby * 16 + by + j) * F.W + mbx * 16 + bx) = prd[j];
+        for (int j = 0; j < 4; j++) *reinterpret_cast<uint32_t *>(P.pred + (size_t)(mby * 16 + by + j) * F.W + mbx * 16 + bx) = o.prd[j];
       }
     }
   }

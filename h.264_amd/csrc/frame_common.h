@@ -1,5 +1,6 @@
-// frame_common.h -- what the frame-stage translation units (frame.hip: MC / finalize / entry points, tq.hip: the fused 4:2:0 / 4:2:2 kernel,
-// frame444.hip: the 4:4:4 stage) share.
+// frame_common.h -- what all three frame-stage translation units (frame.hip: MC / finalize / entry points, tq.hip: the fused 4:2:0 / 4:2:2 kernel,
+// frame444.hip: the 4:4:4 stage) share: the kernels' parameter block, the mode pick, the prediction fetches and mixes. The block body of the
+// two fused kernels and the transform pieces, which frame.hip does not need, are in frame_block.h.
 #pragma once
 #include "jmhip_internal.h"
 
@@ -45,6 +46,29 @@ __device__ __forceinline__ int covering_partition(const jmhip_mb_mode &m, int x4
   }
 }
 
+// the mode of a macroblock that the host gave none: the partitioning with the smallest summed motion cost over the 41 partition costs of the
+// search (me_common.h table order); ties go to the lower mode number
+__device__ __forceinline__ jmhip_mb_mode pick_mode(const int *c)
+{
+  jmhip_mb_mode m;
+  int c8 = 0;
+  for (int b = 0; b < 4; b++) {
+    const int s4 = c[5 + b], s5 = c[9 + 2 * b] + c[10 + 2 * b], s6 = c[17 + 2 * b] + c[18 + 2 * b];
+    const int s7 = c[25 + 4 * b] + c[26 + 4 * b] + c[27 + 4 * b] + c[28 + 4 * b];
+    int best = s4, bm = 4;
+    if (s5 < best) { best = s5; bm = 5; }
+    if (s6 < best) { best = s6; bm = 6; }
+    if (s7 < best) { best = s7; bm = 7; }
+    m.b8mode[b] = (int8_t)bm; c8 += best;
+  }
+  int best = c[0]; m.mode = 1;
+  if (c[1] + c[2] < best) { best = c[1] + c[2]; m.mode = 2; }
+  if (c[3] + c[4] < best) { best = c[3] + c[4]; m.mode = 3; }
+  if (c8 < best) { best = c8; m.mode = 8; }
+  m.pad[0] = m.pad[1] = m.pad[2] = 0;
+  return m;
+}
+
 // one predicted sample from its list-0 / list-1 fetches p0 / p1 (LumaPrediction macroblock.c:880-940, ChromaPrediction4x4 :1768-1830);
 // comp 0 luma, 1 Cb, 2 Cr; s0 / s1 reference slots. The bi-predictive chroma mix uses the luma denominator, as JM does (:1781).
 __device__ __forceinline__ int mix_pred(const FrameDev &F, int pdir, int s0, int s1, int comp, int p0, int p1)
@@ -85,17 +109,12 @@ __device__ __forceinline__ uint32_t fetch4(const uint8_t *p)
   return __builtin_amdgcn_alignbyte(q[1], q[0], (unsigned)(a & 3));
 }
 
-// four luma samples of one row of a 4x4 block predicted from reference `slot` at quarter-pel (xq, yq) [padded units], row rr; ox4 / oy4:
-// the block's offset inside its 8x8 block when the prediction is formed per 8x8 block (8x8 transform), else 0
-__device__ __forceinline__ uint32_t luma_row4(const FrameDev &F, int slot, int xq, int yq, int ox4, int oy4, int rr)
-{
-  const int xpos = clampi(xq >> 2, 0, F.Wp - 1 - 16) + ox4, ypos = clampi(yq >> 2, 0, F.Hp - 1 - 16) + oy4;   // UMVLine4X, refbuf.c:37
-  return fetch4(F.ref_sub[slot] + (size_t)((yq & 3) * 4 + (xq & 3)) * F.Wp * F.Hp + (size_t)(ypos + rr) * F.Wp + xpos);
-}
-// the same from another table of quarter-pel plane stacks with the luma geometry: the 6-tap Cb / Cr planes of a 4:4:4 reference (frame444.hip)
+// four samples of one row of a 4x4 block predicted from reference `slot` of `planes` at quarter-pel (xq, yq) [padded units], row rr. planes: a
+// table of quarter-pel plane stacks with the luma geometry -- F.ref_sub, or the 6-tap Cb / Cr planes of a 4:4:4 reference (F.ref_cb / F.ref_cr).
+// ox4 / oy4: the block's offset inside its 8x8 block when the prediction is formed per 8x8 block (8x8 transform), else 0
 __device__ __forceinline__ uint32_t luma_row4(const FrameDev &F, const uint8_t *const *planes, int slot, int xq, int yq, int ox4, int oy4, int rr)
 {
-  const int xpos = clampi(xq >> 2, 0, F.Wp - 1 - 16) + ox4, ypos = clampi(yq >> 2, 0, F.Hp - 1 - 16) + oy4;
+  const int xpos = clampi(xq >> 2, 0, F.Wp - 1 - 16) + ox4, ypos = clampi(yq >> 2, 0, F.Hp - 1 - 16) + oy4;   // UMVLine4X, refbuf.c:37
   return fetch4(planes[slot] + (size_t)((yq & 3) * 4 + (xq & 3)) * F.Wp * F.Hp + (size_t)(ypos + rr) * F.Wp + xpos);
 }
 

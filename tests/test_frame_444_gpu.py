@@ -143,6 +143,50 @@ def test_frame_stage_444(pkg, name):
 
 
 @pytest.mark.gpu
+def test_y_plane_equals_the_420_stage_luma(pkg):
+    """frame_fused444_kernel and frame_fused_kernel run one block body (frame_block.h) on their own views of it: on the same Y picture, vectors,
+    given modes (8x8 transform on macroblock 0, off on 1, mixed after), CAVLC, adaptive rounding, explicit weights and Y quantisers, plane 0 of the
+    4:4:4 records is the luma of the 4:2:0 records, byte for byte. 80x48: 15 macroblocks, a last workgroup of three live macroblocks and a spare."""
+    inp = build_inputs(pkg, seed=41, w=80, h=48, qp=(28, 28, 28), cavlc=1, ar=1, far=6, given=True, t8="some", weighted=True)
+    n, q = len(inp["mbs"]), inp["quants"]
+    assert n == 15 and inp["t8"][0] and not inp["t8"][1]
+    sub = lambda p: np.ascontiguousarray(p[::2, ::2])
+    ctx = open_context(pkg, inp)
+    try:
+        out = stage(pkg, ctx, inp)
+    finally:
+        ctx.close()
+    ctx = pkg.Context(inp["w"], inp["h"], yuv_format=1, max_refs=1, search_range=R)
+    try:
+        ref, cur = inp["refs"][0], inp["cur"]
+        ctx.ref_upload(0, ref[0], sub(ref[1]), sub(ref[2]))
+        ctx.interp_luma(0)
+        ctx.interp_chroma(0)
+        ctx.cur_upload(cur[0], sub(cur[1]), sub(cur[2]))
+        me = ctx.me_frame(me_params(pkg, inp["qp"][0]), inp["mbs"])
+        ctx.frame_wp_set(inp["wp"])
+        ctx.frame_keep_prediction()
+        chroma_dc = pkg.flat_quant(31, 342, adaptive_rounding=1, adapt_rnd_weight=4, cavlc=1)
+        ctx.residual_frame(np.array([q[0], q[0], chroma_dc, q[3]], dtype=pkg.QUANT_DTYPE), inp["modes"])
+        got, rec, rec8, recon, pred = ctx.residual_download(n, want_results=False), ctx.residual_records(n), ctx.residual_records8(n), ctx.recon_download(), ctx.pred_download()
+    finally:
+        ctx.close()
+    assert np.array_equal(out["me"]["mv"], me["mv"]) and np.array_equal(out["me"]["cost"], me["cost"])
+    r444 = out["records"]
+    # the lists over their cnt entries: frame_fused_kernel does not zero its record first, so what follows a list there is not defined
+    assert np.array_equal(r444["cnt"][:, 0], rec["cnt"][:, :16]), "plane 0 of jmhip_mb_residual444.cnt"
+    listed = np.arange(16) < rec["cnt"][:, :16, None]
+    for f in ("lev", "run"):
+        assert np.array_equal(r444[f][:, 0][listed], rec[f][:, :16][listed]) and not r444[f][:, 0][~listed].any(), "plane 0 of jmhip_mb_residual444.%s" % f
+    for f444, f420 in (("coeff_cost", "coeff_cost"), ("nonzero", "nonzero"), ("fadj", "fadj_y"), ("recon", "recon_y")):
+        assert np.array_equal(r444[f444][:, 0], rec[f420]), "plane 0 of jmhip_mb_residual444.%s" % f444
+    assert r444["lev"][:, 0].any() and r444["fadj"][:, 0].any() and rec8["lev"].any()
+    assert out["records8"][:, 0].tobytes() == rec8.tobytes()
+    assert np.array_equal(out["recon"][0], recon[0]) and np.array_equal(out["pred"][0], pred[0])
+    assert np.array_equal(r444["plane_cbp"][:, 0], got["cbp"] & 15) and np.array_equal(r444["plane_cbp_blk"][:, 0], got["cbp_blk"] & 0xffff)
+
+
+@pytest.mark.gpu
 def test_chain_recon_becomes_the_reference(pkg):
     """jmhip_recon_to_ref after the stage, both interpolations again, a second picture's stage: equal to the helper run on the FIRST picture's
     expected reconstruction."""
